@@ -7,7 +7,10 @@ from a fresh make_data state at qpos0 with qvel[0] = linspace(0, 1, B) and runs 
 launch over the batch. The state is re-initialised inside the kernel each launch, so every launch does
 the full work (nothing is hoisted the way XLA may hoist the reference's loop-invariant fori_loop body).
 
-The same line carries the metric's other half and the other BASELINE configs, each timed in this run:
+A plain run (no --full) sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given and prints the line: nothing else is launched or measured. With --full the same
+line also carries the eager launches timed beside the replay, the kernel's roofline, the metric's other
+half and the other BASELINE configs, each timed in that run:
   * N = 1: the fused PPO env step with its roofline; C3 PPO (src/config.json, 1024 envs x 256 x 4
     epochs x 65,536) throughput and its return@iteration (train_return_avg at iterations 0/25/50/100
     and eval_return at 100, train_ppo.py:321-424); C4 APG (2048 x 128, CG 4/4, backward through the
@@ -16,7 +19,7 @@ The same line carries the metric's other half and the other BASELINE configs, ea
   * N > 1: C5, PPO with 1024 envs per rank and the per-minibatch RCCL all-reduce of both nets'
     gradients timed (train_ppo.py:233-252), next to the sharded speed test.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--envs B]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--envs B] [--dump-outputs DIR] [--full]
         python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 Prints ONE JSON line on rank 0.
 """
@@ -51,8 +54,13 @@ def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--workload", default="all", choices=["all", "speedtest", "ppo"],
-                   help="all: the headline speed test plus every leg; speedtest: the headline only; "
-                        "ppo: the PPO leg alone as the headline (C3 / C5)")
+                   help="all: the headline speed test, plus every leg under --full; speedtest: the headline "
+                        "only; ppo: the PPO leg alone as the headline (C3 / C5)")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: the eager launches, the rooflines, the CPU baseline and the "
+                        "other legs (speed-test extras, PPO C3 / C5, APG C4); off: the headline alone")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned as DIR/<name>.npy")
     p.add_argument("--steps", type=int, default=None, help="timed steps (speedtest launches: 50; ppo iterations: 3)")
     p.add_argument("--warmup", type=int, default=None, help="untimed steps (speedtest: 5; ppo: 2, graph capture)")
     p.add_argument("--speedtest-launch", choices=["graph", "eager"], default="graph",
@@ -242,6 +250,31 @@ def free_gpu():
         torch.cuda.empty_cache()
 
 
+def dump_outputs(path, arrays: dict, rank: int = 0, world: int = 1, limit: int = 64 << 20, seed: int = 0) -> None:
+    """--dump-outputs: what the last timed step returned, as path/<name>.npy in float32 (float64 arrays
+    stay float64), every rank its own shard (<name>.rank<r>.npy at N > 1). At most `limit` bytes in all:
+    an array over its share is cut to a fixed sample, the same sorted `seed`-drawn flat indices every run."""
+    if not path:
+        return
+    os.makedirs(path, exist_ok=True)
+    share = limit // max(1, len(arrays) * world)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"), a)
+
+
+def ppo_outputs(tr, res: dict) -> dict:
+    """What the PPO headline's last timed iteration left with its caller: both nets' parameters and the
+    timed iterations' train_return_avg."""
+    flat = lambda net: torch.cat([p.detach().reshape(-1) for p in net.parameters()]).float().cpu().numpy()  # noqa: E731
+    return {"ppo_policy_params": flat(tr.policy), "ppo_value_params": flat(tr.value),
+            "ppo_train_return_avg": np.asarray(res["train_return_avg"], dtype=np.float64)}
+
+
 # ------------------------------------------------------------------------------------ CPU legs
 def cpu_model_name() -> str:
     try:
@@ -354,9 +387,10 @@ def cpu_baseline(steps: int, speedtest_envs: int = 2048):
 
 # ---------------------------------------------------------------------------------- GPU legs
 def speedtest(args, dist, world, local):
-    """The headline: K speed-test launches over B envs per GPU, with the kernel's roofline."""
+    """The headline: K speed-test launches over B envs per GPU; under --full with the eager launches
+    timed beside the graph replay and the kernel's roofline. Returns (line, (model, sys_), outputs):
+    outputs holds what the last timed step returned."""
     import mjx_amd
-    from mjx_amd import flops as flops_mod
     from mjx_amd import mjx
     model = mjx_amd.load_model(args.model)
     sys_ = mjx.put_model(model)
@@ -365,26 +399,17 @@ def speedtest(args, dist, world, local):
     vel = torch.linspace(0.0, 1.0, B, device=f"cuda:{local}")
     out = torch.empty_like(vel)
     step = lambda: mjx.speedtest_step(sys_, d, vel, out)  # noqa: E731
-    # the timed K steps as one graph replay (eager launches timed beside it, reported as such)
-    ew, ek = timed_launches(step, args.steps, args.warmup, dist)
-    gr = timed_graph(step, args.steps, args.warmup, dist) if getattr(args, "speedtest_launch", "graph") == "graph" else None
+    # the timed K steps as one graph replay (--full: eager launches timed beside it, reported as such)
+    graph = getattr(args, "speedtest_launch", "graph") == "graph"
+    eager = timed_launches(step, args.steps, args.warmup, dist) if args.full or not graph else None
+    gr = timed_graph(step, args.steps, args.warmup, dist) if graph else None
+    if gr is None and eager is None:  # the capture was refused
+        eager = timed_launches(step, args.steps, args.warmup, dist)
     launch = "graph" if gr is not None else "eager"
-    wall, kern_ms = gr if gr is not None else (ew, ek)
+    wall, kern_ms = gr if gr is not None else eager
     wall = max_over_ranks(wall, dist)
-    ew = max_over_ranks(ew, dist)
     value = B * args.steps * world / wall
-    # solver statistics of exactly these states (a forward pass from the same fresh state), for the
-    # algorithmic FLOP count of one env-step (mjx_amd/flops.py, DESIGN.md "Roofline")
-    ds = mjx.make_data(sys_, B, device=local)
-    qv = torch.zeros((B, sys_.nv), device=f"cuda:{local}")
-    qv[:, 0] = vel
-    ds.set("qvel", qv)
-    mjx.forward(sys_, ds)
-    wst = ds.get("stats").double().mean(0).cpu().numpy()
-    fl = flops_mod.step_flops(model, float(wst[0]), float(wst[1]), float(wst[2]), nact=float(wst[3]))
-    achieved_tflops = fl["total"] * B / (kern_ms * 1e-3) / 1e12
-    bytes_per_env = 8  # speed test: 4 B vel in + 4 B qpos[0] out; the state never leaves LDS
-    achieved_gbs = bytes_per_env * B / (kern_ms * 1e-3) / 1e9
+    outputs = {"speedtest_qpos0": out.detach().float().cpu().numpy()}
     line = {
         "metric": "humanoid env-steps/sec (whole node)",
         "value": value,
@@ -404,22 +429,45 @@ def speedtest(args, dist, world, local):
                    "baseline_note": "vs_baseline divides by the README HUMANOID_MJX row (72,618 steps/s, batch 4096)"},
         "build": build_info(),
         "speedtest_launch": launch,
-        "speedtest_eager_ms_per_step": ew / args.steps * 1e3,
-        "speedtest_eager_kernel_ms": ek,
-        "roofline": {"bound": "valu", "achieved": achieved_tflops, "peak": F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved_tflops / F32_PEAK_TFLOPS, "traffic": pmc_traffic(B),
-                     "kernel": SPEEDTEST_KERNEL, "kernel_ms": kern_ms,
-                     "flops_per_env_step": fl["total"],
-                     "workload_mean_ncon_nefc_iter": [float(x) for x in wst[:3]],
-                     "workload_mean_active_rows_per_hessian": float(wst[3]),
-                     "hbm_algorithmic_bytes_per_launch": bytes_per_env * B,
-                     "hbm_achieved_gbs": achieved_gbs, "hbm_frac": achieved_gbs / HBM_PEAK_GBS,
-                     "note": "bound: VALU issue / dependency latency of one env per wave (SQ counters, "
-                             "DESIGN.md 3), priced against the FP32 roof (vector peak = dense MFMA peak); "
-                             "achieved = algorithmic FP32 FLOPs (mjx_amd/flops.py) / kernel time; traffic = "
-                             "HBM bytes per launch from the committed FETCH_SIZE/WRITE_SIZE passes (profiles/)"},
+        "full": bool(args.full),
+        "roofline": speedtest_roofline(model, sys_, vel, kern_ms, local) if args.full else None,
     }
-    return line, (model, sys_)
+    if eager is not None:
+        line["speedtest_eager_ms_per_step"] = max_over_ranks(eager[0], dist) / args.steps * 1e3
+        line["speedtest_eager_kernel_ms"] = eager[1]
+    return line, (model, sys_), outputs
+
+
+def speedtest_roofline(model, sys_, vel, kern_ms, local) -> dict:
+    """The speed-test kernel against the FP32 roof, from a forward pass of its own over the headline's
+    states and the kernel time of the timed steps."""
+    from mjx_amd import flops as flops_mod
+    from mjx_amd import mjx
+    B = int(vel.shape[0])
+    # solver statistics of exactly these states (a forward pass from the same fresh state), for the
+    # algorithmic FLOP count of one env-step (mjx_amd/flops.py, DESIGN.md "Roofline")
+    ds = mjx.make_data(sys_, B, device=local)
+    qv = torch.zeros((B, sys_.nv), device=f"cuda:{local}")
+    qv[:, 0] = vel
+    ds.set("qvel", qv)
+    mjx.forward(sys_, ds)
+    wst = ds.get("stats").double().mean(0).cpu().numpy()
+    fl = flops_mod.step_flops(model, float(wst[0]), float(wst[1]), float(wst[2]), nact=float(wst[3]))
+    achieved_tflops = fl["total"] * B / (kern_ms * 1e-3) / 1e12
+    bytes_per_env = 8  # speed test: 4 B vel in + 4 B qpos[0] out; the state never leaves LDS
+    achieved_gbs = bytes_per_env * B / (kern_ms * 1e-3) / 1e9
+    return {"bound": "valu", "achieved": achieved_tflops, "peak": F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": achieved_tflops / F32_PEAK_TFLOPS, "traffic": pmc_traffic(B),
+            "kernel": SPEEDTEST_KERNEL, "kernel_ms": kern_ms,
+            "flops_per_env_step": fl["total"],
+            "workload_mean_ncon_nefc_iter": [float(x) for x in wst[:3]],
+            "workload_mean_active_rows_per_hessian": float(wst[3]),
+            "hbm_algorithmic_bytes_per_launch": bytes_per_env * B,
+            "hbm_achieved_gbs": achieved_gbs, "hbm_frac": achieved_gbs / HBM_PEAK_GBS,
+            "note": "bound: VALU issue / dependency latency of one env per wave (SQ counters, "
+                    "DESIGN.md 3), priced against the FP32 roof (vector peak = dense MFMA peak); "
+                    "achieved = algorithmic FP32 FLOPs (mjx_amd/flops.py) / kernel time; traffic = "
+                    "HBM bytes per launch from the committed FETCH_SIZE/WRITE_SIZE passes (profiles/)"}
 
 
 def speedtest_extras(args, model, sys_, local):
@@ -925,15 +973,17 @@ def main():
                 "rehearsal": os.environ.get("MJL_BENCH_REHEARSAL") == "1", "build": build_info()}
         if dist is not None:
             line.update(c5_fields(res, world, backend, grad_numel(tr)))
+        dump_outputs(args.dump_outputs, ppo_outputs(tr, res), rank, world)
         if rank == 0:
             print(json.dumps(line), flush=True)
         if dist is not None:
             dist.destroy_process_group()
         return
 
-    line, (model, sys_) = speedtest(args, dist, world, local)
+    line, (model, sys_), outputs = speedtest(args, dist, world, local)
+    dump_outputs(args.dump_outputs, outputs, rank, world)
     legs = {}
-    full = args.workload == "all"
+    full = args.full and args.workload == "all"  # the legs beside the headline
     if world == 1:
         if full and not args.no_extras:
             legs.update(speedtest_extras(args, model, sys_, local))
@@ -951,7 +1001,8 @@ def main():
         del tr
         free_gpu()
     if rank == 0:
-        line["cpu_baseline"] = cpu_baseline(args.cpu_steps, args.envs) if world == 1 and not args.no_cpu else None
+        line["cpu_baseline"] = (cpu_baseline(args.cpu_steps, args.envs)
+                                if args.full and world == 1 and not args.no_cpu else None)
         if line["cpu_baseline"] is not None:
             line["cpu_speedtest_steps_per_s"] = line["cpu_baseline"]["speedtest"]["steps_per_s"]
         line.update(legs)

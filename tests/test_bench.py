@@ -29,6 +29,53 @@ def test_defaults(bench):
     assert (p.steps, p.warmup, p.envs) == (3, 2, 1024)  # C5: 1024 envs per GPU, 8192 over 8
 
 
+def test_plain_run_is_the_default(bench):
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    f = bench.parse(["--full", "--dump-outputs", "d"])
+    assert f.full is True and f.dump_outputs == "d"
+
+
+def test_dump_outputs_files(bench, tmp_path):
+    """<name>.npy in float32 (float64 kept), nothing without a directory; an array over its share of the
+    byte limit is cut to the same sorted sample every run."""
+    import numpy as np
+    a32 = np.arange(12, dtype=np.float32).reshape(3, 4)
+    a64 = np.linspace(0, 1, 5)
+    i32 = np.arange(6, dtype=np.int32)
+    bench.dump_outputs(None, {"a": a32})
+    d = tmp_path / "o"
+    bench.dump_outputs(str(d), {"a": a32, "b": a64, "c": i32})
+    assert sorted(p.name for p in d.iterdir()) == ["a.npy", "b.npy", "c.npy"]
+    assert np.array_equal(np.load(d / "a.npy"), a32) and np.load(d / "a.npy").dtype == np.float32
+    assert np.array_equal(np.load(d / "b.npy"), a64) and np.load(d / "b.npy").dtype == np.float64
+    assert np.load(d / "c.npy").dtype == np.float32
+    big = np.random.default_rng(1).normal(size=1000).astype(np.float32)
+    for sub in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / sub), {"big": big}, limit=400)
+    s1, s2 = np.load(tmp_path / "s1" / "big.npy"), np.load(tmp_path / "s2" / "big.npy")
+    assert s1.shape == (100,) and np.array_equal(s1, s2) and np.isin(s1, big).all()
+    bench.dump_outputs(str(d), {"a": a32}, rank=1, world=2)
+    assert (d / "a.rank1.npy").exists()
+
+
+@pytest.mark.gpu
+def test_plain_speedtest_line_and_outputs(bench):
+    """A plain run's headline: K timed steps, no eager timing or roofline beside it, and the outputs are
+    what one eager speed-test step returns for the same inputs."""
+    import numpy as np
+    from mjx_amd import mjx
+    args = bench.parse(["--steps", "3", "--warmup", "1", "--envs", "96"])
+    line, (model, sys_), outs = bench.speedtest(args, None, 1, 0)
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+    assert line["value"] == pytest.approx(96 * 3 / (line["ms_per_step"] * 3e-3))
+    assert line["roofline"] is None and "speedtest_eager_ms_per_step" not in line and line["full"] is False
+    vel = torch.linspace(0.0, 1.0, 96, device="cuda:0")
+    want = mjx.speedtest_step(sys_, mjx.make_data(sys_, 96, device=0), vel).cpu().numpy()
+    assert set(outs) == {"speedtest_qpos0"} and outs["speedtest_qpos0"].dtype == np.float32
+    assert np.array_equal(outs["speedtest_qpos0"], want)
+
+
 def test_self_launch_command(bench):
     cmd = bench.launch_cmd(["--gpus", "4", "--steps", "7"], 4, 29500)
     assert cmd[1:4] == ["-m", "torch.distributed.run", "--nnodes=1"]

@@ -9,7 +9,8 @@ import pytest
 import mjx_amd
 from mjx_amd import mjcf
 
-REF_MODELS = "/root/reference/models"
+# the reference's two MJCF scenes, stored as fixtures
+REF_MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 @pytest.fixture(scope="module", params=["humanoid_mjx", "humanoid"])
@@ -35,7 +36,6 @@ def test_pair_counts():
     assert sum(mjcf.COL_NCON[k] for k in m1.pair_kind) == 116
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference models not mounted")
 def test_humanoid_xml_pair_filter_by_mujoco_rules():
     """humanoid.xml's 159 candidate pairs, derived here from the XML's body tree (xml.etree, not the
     compiler) by MuJoCo's documented filter (Modeling > Contact > Selection): of C(20,2) = 190 geom
@@ -136,7 +136,6 @@ def test_invweight_and_meaninertia(model):
     assert model.meaninertia == pytest.approx(np.trace(M) / model.nv)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference models not mounted")
 def test_assets_match_fresh_compile():
     for name in mjx_amd.BUILTIN_MODELS:
         fresh = mjcf.compile_xml(os.path.join(REF_MODELS, name + ".xml"))

@@ -134,9 +134,8 @@ def test_descriptor_from_real_mjmodel():
     """Where mujoco is installed: the reference's own MjModel gives the compiler's descriptor."""
     mujoco = pytest.importorskip("mujoco")
     import os
-    path = os.environ.get("MJL_REFERENCE_XML", "")
-    if not os.path.exists(path):
-        pytest.skip("set MJL_REFERENCE_XML to models/humanoid_mjx.xml of the reference")
+    path = os.environ.get("MJL_REFERENCE_XML") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                                                              "humanoid_mjx.xml")
     got = compile_mjmodel(mujoco.MjModel.from_xml_path(path), mujoco)
     want = mjcf.compile_xml(path)
     for k, w in _desc_fields(abi.model_desc(want)).items():

@@ -1,7 +1,8 @@
 """Compile the reference's MJCF models into the package's pre-compiled JSON assets.
 
-Run in the build container (where /root/reference exists):
-    python tools/compile_models.py /root/reference/models
+Run by a maintainer when the models or the compiler change (default source: the MJCF fixtures
+under tests/golden/):
+    python tools/compile_models.py [models-dir]
 The JSON holds only compiled numeric constants (masses, inertias, frames, pair tables ...)
 produced by mjx_amd/mjcf.py, plus the source file's sha256.
 """
@@ -24,4 +25,5 @@ def main(src_dir):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "/root/reference/models")
+    main(sys.argv[1] if len(sys.argv) > 1 else
+         os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))

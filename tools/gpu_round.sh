@@ -4,7 +4,7 @@
 # Steps (each under its own time limit; the first failure ends the call, nothing after it runs):
 #   suite        the GPU test suite (pytest -m gpu)                  -> <out>/pytest.log
 #   smoke        __graft_entry__.smoke()                              -> <out>/smoke.log
-#   bench        the driver's default bench command                  -> <out>/bench.json
+#   bench        the bench with every leg (bench.py --full)          -> <out>/bench.json
 #   trace        rocprofv3 --kernel-trace --stats of the bench       -> <out>/bench_trace/
 #   c5           one rank's C5 update (tools/c5_update_probe.py)      -> <out>/c5.log
 #   c5trace      rocprofv3 kernel trace of the C5 update probe        -> <out>/c5_trace/
@@ -33,9 +33,9 @@ for S in "$@"; do
   case $S in
     suite) step pytest 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 600 python bench.py --gpus 1 --steps 20 --warmup 5 && tail -1 $O/bench.log > $O/bench.json ;;
+    bench) step bench 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 && tail -1 $O/bench.log > $O/bench.json ;;
     trace) step bench_trace 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_trace -o trace -- \
-             python bench.py --gpus 1 --steps 20 --warmup 5
+             python bench.py --full --gpus 1 --steps 20 --warmup 5
            find $O/bench_trace -name '*_kernel_trace.csv' -delete ;;
     c5) step c5 400 python tools/c5_update_probe.py 3 ;;
     c5trace) step c5_trace 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c5_trace -o trace -- \

@@ -1,4 +1,5 @@
-"""Copy one round's measurement record from gpurun_out/prof/ (tools/profile_round.sh) into profiles/.
+"""Copy one round's measurement record from tools/profile_round.sh's output directory into profiles/.
+Usage: python tools/summarize_profiles.py [round] [dir]   (default r1 prof_out)
 
 Writes profiles/<round>_bench.json, <round>_kernel_stats.csv (the rocprofv3 --stats summary of the
 bench command), <round>_pmc_traffic.csv (per-dispatch FETCH_SIZE / WRITE_SIZE of the speed-test
@@ -18,10 +19,11 @@ sys.path.insert(0, os.path.join(ROOT, "mujoco-mjx-lab_amd"))
 from mjx_amd import _lib  # noqa: E402
 
 KERNEL = "step_kernel<mjl::Dims<27, 17, 22, 20, 48, 16>, 2>"
+PROF_DIR = sys.argv[2] if len(sys.argv) > 2 else "prof_out"
 
 
 def one(pattern):
-    hits = glob.glob(os.path.join(ROOT, "gpurun_out", "prof", pattern), recursive=True)
+    hits = glob.glob(os.path.join(ROOT, PROF_DIR, pattern), recursive=True)
     if not hits:
         raise SystemExit(f"missing {pattern}")
     return hits[0]
