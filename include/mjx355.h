@@ -232,6 +232,19 @@ int mjl_env_fill_reset_pool(mjlBatch* batch, const int* dev_n, uint64_t seed, ui
  * per reset; train_ppo.py:150 draws per rollout step). Eager callers leave it unset. */
 int mjl_batch_set_counter_base(mjlBatch* batch, const uint64_t* dev_counter_base);
 
+/* Exponent-carried cotangents for the guarded env-step VJPs (mjl_env_step_vjp_guarded, _vjp_full,
+ * _vjp_replay, _vjp_replay_apg). exp: device int32 [nenv], in/out, true cotangent = stored * 2^exp;
+ * NULL detaches (default). threshold_log2: see DESIGN.
+ * Per env, with e = exp[env] >= 0 on entry: g_qpos / g_qvel / g_qacc_ws / g_aux are read as stored at
+ * 2^-e, g_rew arrives unscaled and is multiplied by 2^-e in the kernel. With m the largest magnitude among
+ * the env's outputs: e = 0 and m < 2^threshold_log2 leaves outputs and exponent as they are (bit-identical
+ * to the detached call); otherwise the outputs are multiplied by 2^-k, k = max(floor(log2 m), -e), and
+ * exp[env] = e + k. Input cotangents whose largest magnitude is at or past 2^threshold_log2 (handed in at
+ * exponent 0) are multiplied by 2^-floor(log2 of it) before the reverse passes, and that power joins e. An env the guard cuts (non-finite outputs, overflowed solve tape) and an env whose input
+ * cotangents are all zero get exp[env] = 0. The first attach on a batch allocates 256 B per env (call it outside
+ * stream capture); every later one is a host-side pointer set, and a captured launch reads the attached address. threshold_log2 in [0, 96], else MJL_ERR_ARG. */
+int mjl_vjp_scale_attach(mjlBatch* batch, int32_t* exp, int threshold_log2);
+
 /* jax.random key modes: element i of a draw / split is threefry2x32(key, (0, i)) (jax >= 0.5
  * default, jax_threefry_partitionable; the reference pins jax==0.7.2, requirements.txt:17), or
  * the pre-0.5 layout (threefry over iota halves). */

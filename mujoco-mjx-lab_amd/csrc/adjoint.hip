@@ -1771,7 +1771,14 @@ struct VjpArgs {
   ApgPostArgs post;  // record: the APG post-step update fused into the launch (post.alive null: none)
   ApgNextArgs next;  // record with post: the next step's observation + policy forward (next.o null: none)
   ApgPolicyBwd pbwd; // replay (ENV): the policy + observation backward added to the state cotangents (P.nl 0: none)
+  // exponent-carried cotangents (mjl_vjp_scale_attach; null: none): per env, in / out, the state cotangents
+  // are stored at 2^-exp of their value; outputs at or past 2^exp_thr are brought back to order 1
+  // input cotangents at or past 2^exp_thr are brought down first, the pointer-read ones through exp_stage
+  int* exp;
+  int exp_thr;
+  float* exp_stage;  // per env kExpStage floats
 };
+constexpr int kExpStage = 64;
 
 // record mode's share of WSA: what the forward leaves there for the reverse passes
 template <class DM> struct WSAR {
@@ -1911,6 +1918,9 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
   if (env >= P.nenv) return;
   const int nq = m->nq, nv = m->nv, nu = m->nu;
   const StateBuf& S = P.s;
+  // exponent-carried cotangents: the env's exponent, and the power of two its input cotangents are brought
+  // down by before the reverse passes (0: as they are)
+  [[maybe_unused]] int e_in = 0, k_in = 0;
   if constexpr (TM != 1) {  // the VJP is linear in the cotangents: all-zero in -> all-zero out, without
      // the recompute (envs past termination in an APG rollout; also keeps 0 * non-finite out of their outputs)
     // clamped-index loads (no branch around each): all issue before the first compare
@@ -1918,7 +1928,12 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
     const int ia = lane < MJL_AUX_DIM ? lane : MJL_AUX_DIM - 1;
     const float cq = nq > 0 ? V.g_qpos[(size_t)env * nq + iq] : 0.f, cv = nv > 0 ? V.g_qvel[(size_t)env * nv + iv] : 0.f;
     const float cw = (V.g_ws && nv > 0) ? V.g_ws[(size_t)env * nv + iv] : 0.f;
-    const float cr = ENV ? V.g_rew[env] : 0.f, ca = ENV ? V.g_aux[(size_t)env * MJL_AUX_DIM + ia] : 0.f;
+    float cr = ENV ? V.g_rew[env] : 0.f;
+    const float ca = ENV ? V.g_aux[(size_t)env * MJL_AUX_DIM + ia] : 0.f;
+    if (ENV && V.exp) {  // the reward's cotangent arrives unscaled
+      e_in = V.exp[env];
+      cr = ldexpf(cr, -e_in);
+    }
     bool nz = (lane < nq && cq != 0.f) || (lane < nv && (cv != 0.f || cw != 0.f));
     if (ENV) nz = nz || (lane == 0 && cr != 0.f) || (lane < MJL_AUX_DIM && ca != 0.f);
     if (__ballot(nz) == 0ull) {
@@ -1927,7 +1942,18 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
       if (lane < nu) V.o_ctrl[(size_t)env * nu + lane] = 0.f;
       if (ENV && lane < MJL_AUX_DIM) V.o_aux[(size_t)env * MJL_AUX_DIM + lane] = 0.f;
       if (V.o_ws && lane < nv) V.o_ws[(size_t)env * nv + lane] = 0.f;
+      if (V.exp && lane == 0) V.exp[env] = 0;
       return;
+    }
+    if (ENV && V.exp) {
+      // input cotangents at or past the threshold (handed in at exponent 0; a sweep's own arrive in [1, 2)
+      // plus what the policy adds) come down to order 1 first: the reverse passes' intermediates stand
+      // orders of magnitude above their inputs (unrolled CG: more than 2^28) and would leave fp32 range
+      // inside the step, where no rescale of the outputs reaches
+      auto mag = [](float x) { return __float_as_uint(x) & 0x7fffffffu; };
+      const unsigned mb = wmax_u(max(max(mag(cq), mag(cv)), max(max(mag(cw), mag(ca)), mag(cr))));
+      const int mi = (int)(mb >> 23) - 127;
+      if (mb < 0x7f800000u && mi >= V.exp_thr) k_in = mi;
     }
   }
   float* scr_env = V.scratch + (size_t)env * (size_t)V.scratch_stride;
@@ -2067,13 +2093,32 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
     }
   }
   const float* gq = V.g_qpos + (size_t)env * nq;
-  if (lane < nv) A->vtmp[lane] = V.g_qvel[(size_t)env * nv + lane];
-  SYNC();
-  if (ENV) adj_env<D>(m, W, A, (CP)P.env, (const float*)aux, V.g_rew[env], V.g_aux + (size_t)env * MJL_AUX_DIM, lane);
+  const float* gax = ENV ? V.g_aux + (size_t)env * MJL_AUX_DIM : nullptr;
+  if (k_in != 0) {  // (wave-uniform) the pointer-read inputs, brought down by 2^-k_in, through the env's staging row
+    static_assert(MJL_MAXQ + MJL_AUX_DIM <= kExpStage, "staging row: qpos' and aux' cotangents");
+    float* st = V.exp_stage + (size_t)env * kExpStage;
+    if (lane < nq) st[lane] = ldexpf(gq[lane], -k_in);
+    if (ENV && lane < MJL_AUX_DIM) st[MJL_MAXQ + lane] = ldexpf(gax[lane], -k_in);
+    gq = st;
+    gax = st + MJL_MAXQ;
+  }
+  if (lane < nv) {
+    const float g = V.g_qvel[(size_t)env * nv + lane];
+    A->vtmp[lane] = k_in != 0 ? ldexpf(g, -k_in) : g;
+  }
+  SYNC();  // (also: the staging row's stores before its loads, same workgroup)
+  if (ENV) {
+    const float gr = V.g_rew[env];
+    adj_env<D>(m, W, A, (CP)P.env, (const float*)aux, V.exp ? ldexpf(gr, -e_in - k_in) : gr, gax, lane);
+  }
+  e_in += k_in;  // what the outputs are stored at before the rescale below
   STAMP(14, lane);
   // the dense arrays (mats): in LDS, or (lean) in the slot's workspace image and A part in global memory
   adj_integrate<D>(m, W, A, mats, gq, unr, lane);
-  if (V.g_ws && lane < nv) A->qaccb[lane] += V.g_ws[(size_t)env * nv + lane];  // output warm start = qacc
+  if (V.g_ws && lane < nv) {  // output warm start = qacc
+    const float g = V.g_ws[(size_t)env * nv + lane];
+    A->qaccb[lane] += k_in != 0 ? ldexpf(g, -k_in) : g;
+  }
   SYNC();
   STAMP(2, lane);
   if (unr) adj_solver_unrolled<D>(m, W, A, mats, R, scr_adj, P.gmax_efc, tp, lane);
@@ -2112,7 +2157,7 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
     if (ENV && lane < MJL_AUX_DIM) A->auxb[lane] = nan;
     SYNC();
   }
-  if (V.nonfinite) {  // cut an env whose cotangents overflowed from the gradient (APG guard)
+  if (V.nonfinite && !V.exp) {  // cut an env whose cotangents overflowed from the gradient (APG guard)
     bool bad = (lane < nq && !isfinite(A->qposb[lane])) || (lane < nv && !isfinite(A->qvelb[lane])) ||
                (lane < nu && !isfinite(A->ctrlb[lane])) || (ENV && lane < MJL_AUX_DIM && !isfinite(A->auxb[lane])) ||
                (lane < nv && !isfinite(A->wsb[lane])) || tape_over;
@@ -2131,6 +2176,8 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
   // adds it to them after); the smooth-dynamics scratch (dead after the reverse passes) holds its rows
   const bool pol = ENV && TM == 2 && V.pbwd.P.nl > 0;
   LDSA float* gsrc = (LDSA float*)W->cinert;  // [32] action cotangent by action, [2][64] layer rows, [64] obs part
+  float oc = 0.f;  // this lane's action cotangent and where it goes (scaled outputs: stored after the rescale)
+  int oc_at = lane;
   if (lane < nu) {
     if (ENV) {  // ctrl = clip(flip ? act[perm] * sign : act, -1, 1)
       const mjlEnvConfig* c = P.env;
@@ -2141,8 +2188,10 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
       const float ga = (a > -1.f && a < 1.f) ? sg * A->ctrlb[lane] : 0.f;
       V.o_ctrl[(size_t)env * nu + src] = ga;
       if (pol) gsrc[src] = ga;
+      oc = ga; oc_at = src;
     } else {
       V.o_ctrl[(size_t)env * nu + lane] = A->ctrlb[lane];
+      oc = A->ctrlb[lane];
     }
   }
   float gq_add = 0.f, gv_add = 0.f;
@@ -2187,10 +2236,39 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
     if (lane < nq) gq_add = ggs[lane];
     if (lane < nv) gv_add = ggs[nq + lane];
   }
-  if (lane < nq) V.o_qpos[(size_t)env * nq + lane] = pol ? A->qposb[lane] + gq_add : A->qposb[lane];
-  if (lane < nv) V.o_qvel[(size_t)env * nv + lane] = pol ? A->qvelb[lane] + gv_add : A->qvelb[lane];
-  if (V.o_ws && lane < nv) V.o_ws[(size_t)env * nv + lane] = A->wsb[lane];
-  if (ENV && lane < MJL_AUX_DIM) V.o_aux[(size_t)env * MJL_AUX_DIM + lane] = A->auxb[lane];
+  float oq = 0.f, ov = 0.f, ow = 0.f, oa = 0.f;
+  if (lane < nq) oq = pol ? A->qposb[lane] + gq_add : A->qposb[lane];
+  if (lane < nv) { ov = pol ? A->qvelb[lane] + gv_add : A->qvelb[lane]; ow = A->wsb[lane]; }
+  if (ENV && lane < MJL_AUX_DIM) oa = A->auxb[lane];
+  if (V.exp) {
+    // exponent-carried cotangents: the wave's largest output magnitude m (as its bit pattern: non-finite
+    // sorts above every finite value) decides a power-of-two rescale of all the env's outputs; the guard
+    // then sees the rescaled values
+    auto mag = [](float x) { return __float_as_uint(x) & 0x7fffffffu; };
+    const unsigned mb = wmax_u(max(max(max(mag(oq), mag(ov)), max(mag(ow), mag(oa))), mag(oc)));
+    const int me = (int)(mb >> 23) - 127;  // floor(log2 m) of a normal m
+    int e_out = e_in;
+    if (mb < 0x7f800000u && mb != 0u && !(e_in == 0 && me < V.exp_thr)) {
+      const int k = max(me, -e_in);  // m to [1, 2), or back to scale 1 where that comes first
+      oq = ldexpf(oq, -k); ov = ldexpf(ov, -k); ow = ldexpf(ow, -k); oa = ldexpf(oa, -k); oc = ldexpf(oc, -k);
+      e_out = e_in + k;
+    }
+    if (V.nonfinite) {  // the guard, as above, behind the rescale
+      const bool bad = !isfinite(oq) || !isfinite(ov) || !isfinite(ow) || !isfinite(oa) || !isfinite(oc) ||
+                       (lane < nu && !isfinite(A->ctrlb[lane])) || tape_over;  // (ctrlb: also where the clip masks it)
+      if (__ballot(bad) != 0ull) {
+        oq = ov = ow = oa = oc = 0.f;
+        e_out = 0;
+        if (lane == 0) atomicAdd(V.nonfinite, 1.f);
+      }
+    }
+    if (lane < nu) V.o_ctrl[(size_t)env * nu + oc_at] = oc;
+    if (lane == 0) V.exp[env] = e_out;
+  }
+  if (lane < nq) V.o_qpos[(size_t)env * nq + lane] = oq;
+  if (lane < nv) V.o_qvel[(size_t)env * nv + lane] = ov;
+  if (V.o_ws && lane < nv) V.o_ws[(size_t)env * nv + lane] = ow;
+  if (ENV && lane < MJL_AUX_DIM) V.o_aux[(size_t)env * MJL_AUX_DIM + lane] = oa;
   }
 }
 

@@ -67,6 +67,9 @@ struct mjlBatch {
   TapeDims unr_dims;
   int adj_stride, adj_row_floats;
   const unsigned long long* ctr_base;  // device RNG counter base (mjl_batch_set_counter_base), or null
+  int* vjp_exp;       // per-env cotangent exponents of the guarded env-step VJPs (mjl_vjp_scale_attach), or null
+  int vjp_exp_thr;    // log2 of the output magnitude from which an env's cotangents are rescaled
+  float* d_exp_stage; // per env kExpStage floats: rescaled input cotangents (allocated by the first attach)
   const uint32_t* reset_keys;           // per-env jax.random reset keys (mjl_env_set_reset_keys), or null
   int key_mode;
   float* d_vtape;  // MJL_OPT_VJP_TAPE: slots x nenv x vtape_stride floats (record / replay), or null
@@ -439,6 +442,7 @@ void mjl_batch_destroy(mjlBatch* B) {
   (void)hipFree(B->d_state); (void)hipFree(B->d_model); (void)hipFree(B->d_env); (void)hipFree(B->d_scratch);
   (void)hipFree(B->d_adj_scratch);
   (void)hipFree(B->d_unr);
+  (void)hipFree(B->d_exp_stage);
   (void)hipFree(B->d_rs); (void)hipFree(B->d_pool_ctl); (void)hipFree(B->d_vtape);
   delete B;
 }
@@ -761,6 +765,20 @@ int mjl_batch_set_counter_base(mjlBatch* B, const uint64_t* dev_counter_base) {
   return MJL_OK;
 }
 
+int mjl_vjp_scale_attach(mjlBatch* B, int32_t* exp, int threshold_log2) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (exp && (threshold_log2 < 0 || threshold_log2 > 96))
+    return fail(MJL_ERR_ARG, "threshold_log2 %d outside [0, 96]", threshold_log2);
+  if (exp && !B->d_exp_stage) {  // the first attach allocates (outside stream capture); later ones only set pointers
+    HIPCHK(hipSetDevice(B->device));
+    hipError_t e = hipMalloc(&B->d_exp_stage, (size_t)kExpStage * B->nenv * sizeof(float));
+    if (e != hipSuccess) { B->d_exp_stage = nullptr; return fail(MJL_ERR_HIP, "cotangent staging: %s", hipGetErrorString(e)); }
+  }
+  B->vjp_exp = exp;
+  B->vjp_exp_thr = threshold_log2;
+  return MJL_OK;
+}
+
 int mjl_env_set_reset_keys(mjlBatch* B, const uint32_t* dev_keys, int mode) {
   if (!B) return fail(MJL_ERR_ARG, "null batch");
   if (dev_keys && mode != MJL_RNG_JAX_PARTITIONABLE && mode != MJL_RNG_JAX_ORIGINAL)
@@ -811,6 +829,7 @@ template <bool ENV, int TM = 0> static int launch_vjp(mjlBatch* B, const VjpArgs
   V.scratch = B->d_adj_scratch;
   V.scratch_stride = B->adj_stride;
   V.row_floats = B->adj_row_floats;
+  if (ENV && TM != 1) { V.exp = B->vjp_exp; V.exp_thr = B->vjp_exp_thr; V.exp_stage = B->d_exp_stage; }
   dim3 grid(B->nenv), block(64);
   // the replay on the humanoid dims takes the lean layout (20 KB of LDS: one round of 8 envs per CU;
   // MJL_VJP_LEAN=0 keeps the full one, for A/B)

@@ -147,6 +147,18 @@ INL float wsum(float v) {
   v += dpp0<0x143, 0xC>(v);  // row_bcast31
   return rdlane(v, 63);
 }
+// max over the 64 lanes of an unsigned value, result in every lane (wsum's steps; 0 is max's identity)
+INL unsigned wmax_u(unsigned u) {
+  float v = __uint_as_float(u);
+  auto mx = [](float a, float b) { return __uint_as_float(max(__float_as_uint(a), __float_as_uint(b))); };
+  v = mx(v, dppm<0xB1>(v));
+  v = mx(v, dppm<0x4E>(v));
+  v = mx(v, dppm<0x141>(v));
+  v = mx(v, dppm<0x140>(v));
+  v = mx(v, dpp0<0x142, 0xA>(v));
+  v = mx(v, dpp0<0x143, 0xC>(v));
+  return __float_as_uint(rdlane(v, 63));
+}
 INL unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
 // The lane index through an opaque move: lane masks compared against it are computed where they
 // are used. Against a plain lane index the compiler hoists a loop's 27 mask compares out of the

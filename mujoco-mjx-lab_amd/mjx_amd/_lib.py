@@ -30,7 +30,7 @@ EXPORTS = [
     "mjl_apg_obs", "mjl_apg_post", "mjl_apg_obs_vjp", "mjl_env_step_record", "mjl_env_step_record_apg",
     "mjl_env_step_record_apg_next", "mjl_env_record_fused", "mjl_env_step_vjp_replay", "mjl_env_step_vjp_replay_apg",
     "mjl_ppo_loss_scratch", "mjl_ppo_surrogate", "mjl_mse", "mjl_gather_rows", "mjl_adam",
-    "mjl_adam_dev",
+    "mjl_adam_dev", "mjl_vjp_scale_attach",
     "mjl_colsum_batched_scratch", "mjl_colsum_batched", "mjl_tanh_bwd_colsum_batched", "mjl_slice_sum_batched",
     "mjl_mse_strided", "mjl_ppo_surrogate_clipped", "mjl_bias_act", "mjl_adam_multi",
     "mjl_gather_rows_indexed", "mjl_slice_sum_multi", "mjl_tanh_bwd_colsum_partials", "mjl_twin_loss_head_blocks", "mjl_twin_loss_head",
@@ -127,6 +127,7 @@ def lib() -> C.CDLL:
     L.mjl_apg_obs_vjp.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     L.mjl_batch_set_counter_base.argtypes = [vp, vp]
     L.mjl_env_set_reset_keys.argtypes = [vp, vp, i32]
+    L.mjl_vjp_scale_attach.argtypes = [vp, vp, i32]
     L.mjl_env_step_vjp_guarded.argtypes = [vp] + [vp] * 10 + [vp]
     L.mjl_state_size.argtypes = [vp]
     L.mjl_get_state.argtypes = [vp, vp, vp]

@@ -19,6 +19,11 @@ OPT_RESET_POOL = 3  # slots per env of the reset pool (mjl_env_fill_reset_pool)
 OPT_VJP_TAPE = 4  # slots of the APG VJP tape (mjl_env_step_record / mjl_env_step_vjp_replay)
 OPT_VJP_UNROLLED = 2  # step VJPs differentiate the solver iterations as executed (jax.grad semantics)
 
+# exponent-carried cotangents (mjl_vjp_scale_attach): log2 of the output magnitude from which an env's
+# cotangents are rescaled, and the range the library accepts
+VJP_SCALE_THRESHOLD_LOG2 = 40
+VJP_SCALE_THRESHOLD_RANGE = (0, 96)
+
 FIELD = {
     "qpos": 0, "qvel": 1, "qacc_warmstart": 2, "time": 3, "ctrl": 4, "qacc": 5, "xpos": 6,
     "xquat": 7, "qfrc_actuator": 8, "sensordata": 9, "aux": 10, "stats": 11, "qfrc_bias": 12,

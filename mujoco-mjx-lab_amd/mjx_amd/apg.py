@@ -151,6 +151,71 @@ class NativeAPGPolicy:
         return gx
 
 
+def _pow2(n: torch.Tensor) -> torch.Tensor:
+    """2^n as fp64, exactly (built from the exponent bits; n an integer tensor, clamped to fp64's normal range)."""
+    return ((n.to(torch.int64).clamp(-1022, 1023) + 1023) << 52).view(torch.float64)
+
+
+def _ldexp(x: torch.Tensor, n: torch.Tensor) -> torch.Tensor:
+    """x * 2^n through fp64: exact wherever the result is a normal number of x's dtype."""
+    return (x.double() * _pow2(n)).to(x.dtype)
+
+
+class CotangentScale:
+    """Exponent-carried cotangents of one reverse sweep: per env an int32 exponent e >= 0
+    rides beside the state cotangents, true value = stored * 2^e, so a product of per-step gains that
+    leaves fp32 range stays representable. After each step's VJP, with m the env's largest output magnitude:
+    e = 0 and m < 2^thr changes nothing; otherwise every output is multiplied by 2^-k,
+    k = max(floor(log2 m), -e), and e += k. Powers of two only: the scaled sweep is the unscaled one
+    bit for bit wherever neither over- nor underflows. An env that rescales natively
+    (`native_vjp_scale`: HumanoidAPGEnv, in the VJP kernel) gets the exponents attached; any other env
+    gets the same rule here, around its step_vjp. (The kernel also brings input cotangents at or past
+    2^thr down before its reverse passes; a sweep never hands it such inputs, its own outputs being in
+    [1, 2), so the torch form has no such step.)"""
+
+    def __init__(self, env, horizon: int, device, threshold_log2: int):
+        self.env, self.thr = env, int(threshold_log2)
+        self.native = bool(getattr(env, "native_vjp_scale", False))
+        self.e = torch.zeros(env.num_envs, dtype=torch.int32, device=device)
+        self.rec = torch.zeros((horizon, env.num_envs), dtype=torch.int32, device=device)  # e after step t
+        if self.native:
+            env.attach_vjp_scale(self.e, self.thr)
+
+    def close(self):
+        if self.native:
+            self.env.attach_vjp_scale(None, self.thr)
+
+    def grew(self, grew: torch.Tensor) -> torch.Tensor:
+        """The reward cotangent as the VJP call takes it (the native kernel scales it itself)."""
+        return grew if self.native else _ldexp(grew, -self.e)
+
+    def rescale(self, outs):
+        """The rule on one step's outputs (a tuple of [B, n] cotangents, None entries kept)."""
+        if self.native:
+            return outs
+        m = torch.stack([o.detach().abs().amax(1).double() for o in outs if o is not None]).amax(0)
+        me = torch.frexp(m)[1] - 1  # floor(log2 m) of a finite m > 0
+        e = self.e
+        on = torch.isfinite(m) & (m > 0) & ~((e == 0) & (me < self.thr))
+        k = torch.where(on, torch.maximum(me, -e), torch.zeros_like(e))
+        self.e.copy_(e + k)
+        return tuple(None if o is None else _ldexp(o, -k[:, None]) for o in outs)
+
+    def cut(self, ok: torch.Tensor):
+        """Envs the torch guard zeroed start again from exponent 0 (the native guard does the same)."""
+        self.e.mul_(ok.to(self.e.dtype))
+
+    def record(self, t: int):
+        self.rec[t].copy_(self.e)
+
+    def finish(self, gas):
+        """The action cotangents of all steps at the one scale 2^-E, E the largest exponent of the sweep
+        (rows that underflow are below fp32's resolution of the sum), E, and the envs whose exponent left 0."""
+        E = self.rec.amax()
+        g = _ldexp(torch.cat(gas), (self.rec.reshape(-1) - E)[:, None])
+        return g, E, (self.rec.amax(0) > 0).sum()
+
+
 def apg_normalize(rms: RunningMeanStd, x: torch.Tensor) -> torch.Tensor:
     """train_apg.py:171-176 (note sqrt(var) + 1e-8, unlike PPO's sqrt(var + 1e-8))."""
     return torch.clamp((x - rms.mean) / (torch.sqrt(rms.var) + 1e-8), -10.0, 10.0)
@@ -162,11 +227,19 @@ class APGTrainer:
     through `HumanoidAPGEnv`, or the differentiable stand-in of the CPU tests)."""
 
     def __init__(self, cfg, env, device="cuda", dist=None, out_dir: Optional[str] = None, use_graph: bool = True,
-                 vjp_tape: bool = True):
+                 vjp_tape: bool = True, scale_cotangents: bool = False, scale_threshold_log2: Optional[int] = None):
         """vjp_tape: the forward rollout records each step's workspace in HBM (mjl_env_step_record,
         ~50 KB per env-step: 6 GB at 2048 x 128) and the reverse sweep replays it
-        (mjl_env_step_vjp_replay) instead of restoring the state and recomputing the step."""
+        (mjl_env_step_vjp_replay) instead of restoring the state and recomputing the step.
+        scale_cotangents: the reverse sweep carries a per-env power-of-two exponent beside the cotangents
+        (CotangentScale), so an env whose chained step Jacobians leave fp32 range stays in the gradient
+        instead of being cut by the guard; the gradient then lives at 2^-E until the clip (update())."""
+        from . import abi
         self.cfg, self.env, self.dist = cfg, env, dist
+        self.scale_cotangents = bool(scale_cotangents)
+        self.scale_threshold_log2 = int(abi.VJP_SCALE_THRESHOLD_LOG2 if scale_threshold_log2 is None
+                                        else scale_threshold_log2)
+        self.last_scale = None  # (E, envs whose exponent left 0) of the last sweep, device tensors
         self.use_graph = bool(use_graph)
         self.vjp_tape = bool(vjp_tape)
         self._graphs, self._warm = {}, set()
@@ -234,8 +307,8 @@ class APGTrainer:
             used = env.counter - c0 + 1
             env.counter = c0  # capture ran nothing; the replay below draws the reset
             self._graphs[key] = (graph, out, [p.grad for p in self.policy.parameters()], used,
-                                 self.last_reverse_inputs)
-        graph, out, grads, used, self.last_reverse_inputs = self._graphs[key]
+                                 self.last_reverse_inputs, self.last_scale)
+        graph, out, grads, used, self.last_reverse_inputs, self.last_scale = self._graphs[key]
         env.ctr_base.fill_(env.counter)
         graph.replay()
         env.counter += used
@@ -245,6 +318,8 @@ class APGTrainer:
         return out
 
     def _loss_and_grad(self, use_norm: bool, per_step_param_grad: bool = False, graph: bool = False):
+        if self.scale_cotangents and per_step_param_grad:
+            raise ValueError("scale_cotangents: the parameter gradient is taken once, at the sweep's one scale")
         if getattr(self.env, "native_apg", False) and not per_step_param_grad:
             return self._loss_and_grad_native(use_norm, graph)
         return self._loss_and_grad_torch(use_norm, per_step_param_grad, graph)
@@ -324,26 +399,31 @@ class APGTrainer:
         gas = [None] * H
         # the policy + observation backward in the replay launch (MJL_APG_FUSED_BWD=0: their own launch)
         fused_bwd = taped and fused and os.environ.get("MJL_APG_FUSED_BWD", "1") != "0"
+        sc = CotangentScale(env, H, dev, self.scale_threshold_log2) if self.scale_cotangents else None
         for t in range(H - 1, -1, -1):
             if fused_bwd:  # slot t's reverse passes, then the policy's and the observation's backward
                 gq, gv, gws, ga, gaux = nat.replay_bwd(env, t, acts[t].detach(), gq, gv, gws, grew_all[t], gaux,
                                                        nonfinite, [y[t] for y in ys_all], o_all[t], snap[t], self.rms,
                                                        use_norm)
                 gas[t] = ga
+                if sc is not None:
+                    sc.record(t)
                 if self.diag is not None and not graph:
                     e = (ga.double() ** 2).sum(1)
                     self.diag["ga_sq"] = e if t == H - 1 else self.diag["ga_sq"] + e
                 continue
+            grew = grew_all[t] if sc is None else sc.grew(grew_all[t])
             if taped:  # the reverse passes from slot t: no state restore, no recompute
-                gq, gv, gws, ga, gaux = env.step_vjp_replay(t, acts[t].detach(), gq, gv, gws, grew_all[t], gaux,
-                                                            nonfinite)
+                gq, gv, gws, ga, gaux = env.step_vjp_replay(t, acts[t].detach(), gq, gv, gws, grew, gaux, nonfinite)
             else:
                 env.set_state(tape[t], tape[t + 1] if t + 1 < H else final)
                 if gws is not None:
-                    gq, gv, gws, ga, gaux = env.step_vjp_full(acts[t].detach(), gq, gv, gws, grew_all[t], gaux,
-                                                              nonfinite)
+                    gq, gv, gws, ga, gaux = env.step_vjp_full(acts[t].detach(), gq, gv, gws, grew, gaux, nonfinite)
                 else:
-                    gq, gv, ga, gaux = env.step_vjp(acts[t].detach(), gq, gv, grew_all[t], gaux, nonfinite)
+                    gq, gv, ga, gaux = env.step_vjp(acts[t].detach(), gq, gv, grew, gaux, nonfinite)
+            if sc is not None:  # (cotangents the policy backward adds below ride at the same exponent)
+                gq, gv, gws, ga, gaux = sc.rescale((gq, gv, gws, ga, gaux))
+                sc.record(t)
             if fused:
                 nat.backward_obs_vjp(env, ga, [y[t] for y in ys_all], o_all[t], snap[t], self.rms, use_norm, gq, gv)
             else:
@@ -356,7 +436,13 @@ class APGTrainer:
             if self.diag is not None and not graph:  # sum over steps of |d loss / d a_t|^2 per env
                 e = (ga.double() ** 2).sum(1)
                 self.diag["ga_sq"] = e if t == H - 1 else self.diag["ga_sq"] + e
-        torch.autograd.backward(self.policy(on_all.reshape(H * B, w)), grad_tensors=torch.cat(gas))
+        if sc is not None:  # the gradient at 2^-E (diag's ga_sq above: in the stored units)
+            sc.close()
+            g_all, E, scaled = sc.finish(gas)
+            self.last_scale = (E, scaled)
+        else:
+            g_all = torch.cat(gas)
+        torch.autograd.backward(self.policy(on_all.reshape(H * B, w)), grad_tensors=g_all)
         dropped = torch.stack([dropped_e.sum(), nonfinite[0]])  # (forward guard, reverse guard)
         # the reward cotangents and actions of the last rollout (graph-owned under capture: they hold
         # the last replay's values), for timing the replay VJP on the trainer's own workload (bench.py)
@@ -432,20 +518,27 @@ class APGTrainer:
         # unrolled VJP: the next solve depends on the carried qacc_warmstart, so its cotangent rides along
         gws = torch.zeros((B, env.nv), device=self.device) if getattr(env, "vjp_carries_ws", False) else None
         gas = [None] * H
+        sc = CotangentScale(env, H, self.device, self.scale_threshold_log2) if self.scale_cotangents else None
         for t in range(H - 1, -1, -1):
             # the VJP recomputes the step to find its converged active set; the solution the forward
             # step reached (the next tape entry's qacc_warmstart) seeds that solve: ~1 Newton iteration
             env.set_state(tape[t], tape[t + 1] if t + 1 < H else final)
             grew = -discs[t] / B
+            if sc is not None:
+                grew = sc.grew(grew)
             # an env whose cotangents overflow (a state blowing up while still in the loss) is cut from
             # the gradient at this step, like the forward guard above (in the kernel when it can)
             if gws is not None:
                 gq, gv, gws, ga, gaux = env.step_vjp_full(acts[t].detach(), gq, gv, gws, grew, gaux, nonfinite)
             else:
                 gq, gv, ga, gaux = env.step_vjp(acts[t].detach(), gq, gv, grew, gaux, nonfinite)
+            if sc is not None:  # rescale, then the guard
+                gq, gv, gws, ga, gaux = sc.rescale((gq, gv, gws, ga, gaux))
             if not guarded:
                 ok = torch.isfinite(gq).all(1) & torch.isfinite(gv).all(1) & torch.isfinite(ga).all(1)
                 rev_dropped = rev_dropped + (~ok).sum()
+                if sc is not None:
+                    sc.cut(ok)
                 gq = torch.where(ok[:, None], gq, torch.zeros_like(gq))
                 gv = torch.where(ok[:, None], gv, torch.zeros_like(gv))
                 ga = torch.where(ok[:, None], ga, torch.zeros_like(ga))
@@ -465,12 +558,18 @@ class APGTrainer:
             else:
                 og, = torch.autograd.grad(acts[t], obs_leaves[t], grad_outputs=ga)
             gas[t] = ga
+            if sc is not None:
+                sc.record(t)
             gq = gq + og[:, :env.nq]
             gv = gv + og[:, env.nq:]
         # parameter gradient: sum_t (d a_t / d theta)^T ga_t as one forward + backward over the H * B
         # policy inputs of the rollout (the same inputs; per step it was H small backward passes)
+        if sc is not None:
+            sc.close()
+            g_all, E, scaled = sc.finish(gas)
+            self.last_scale = (E, scaled)
         if not per_step_param_grad:
-            torch.autograd.backward(self.policy(torch.cat(pol_in)), grad_tensors=torch.cat(gas))
+            torch.autograd.backward(self.policy(torch.cat(pol_in)), grad_tensors=g_all if sc is not None else torch.cat(gas))
         dropped = torch.stack([dropped.to(torch.float32), (nonfinite[0] if guarded else rev_dropped).to(torch.float32)])
         return loss.detach(), (rsum / H).detach(), (torch.stack(obs_traj), torch.stack(in_loss)), dropped
 
@@ -484,13 +583,30 @@ class APGTrainer:
         params = list(self.policy.parameters())
         g = _flat_grads(params)
         stats = torch.cat([torch.stack([loss, mean_r]), dropped.to(loss.dtype).reshape(2)])
+        E = None
+        if self.scale_cotangents:  # g is the gradient at 2^-E (CotangentScale.finish)
+            E, scaled = self.last_scale
+            stats = torch.cat([stats, scaled.to(stats.dtype).reshape(1)])
+            if self.dist is not None:  # every rank's gradient to the largest exponent among the ranks
+                Eg = E.clone()
+                self.dist.all_reduce(Eg, op=self.dist.ReduceOp.MAX)
+                g = _ldexp(g, E - Eg)
+                E = Eg
         if self.dist is not None:
             self.dist.all_reduce(g)
             g /= self.world
             self.dist.all_reduce(stats)
             stats[:2] /= self.world
         gnorm = torch.linalg.vector_norm(g.double())  # fp64: an fp32 sum of squares overflows on blow-ups
-        g = g * torch.clamp(cfg.grad_clip / (gnorm + 1e-16), max=1.0).to(g.dtype)  # optax.clip_by_global_norm
+        if E is None:
+            g = g * torch.clamp(cfg.grad_clip / (gnorm + 1e-16), max=1.0).to(g.dtype)  # optax.clip_by_global_norm
+        else:
+            # the same clip of g * 2^E: one factor min(2^E, clip 2^E / norm), applied as the factor's mantissa
+            # rounded to g's dtype (what the line above multiplies by when E = 0) and an exact power of two,
+            # so the factor never has to exist in fp32 (2^E and 1 / norm each can lie outside its range)
+            gnorm = gnorm * _pow2(E)
+            mant, p = torch.frexp(torch.clamp(cfg.grad_clip / (gnorm + 1e-16), max=1.0))
+            g = _ldexp(g * mant.to(g.dtype), E + p)
         _set_grads(params, g)
         self.opt.step()
         frozen = getattr(cfg, "rms_freeze_after", None) is not None and step > cfg.rms_freeze_after
@@ -510,7 +626,10 @@ class APGTrainer:
                 "grad_norm": float(gnorm), "env_steps_per_sec": steps / dt,
                 "nonfinite_envs": int(stats[2]) + int(stats[3]),  # dropped from the loss, either guard
                 "forward_dropped_envs": int(stats[2]),  # state / reward non-finite or |qvel| > diverge_qvel
-                "reverse_nonfinite_envs": int(stats[3])}  # cotangents overflowed in the VJP sweep
+                "reverse_nonfinite_envs": int(stats[3]),  # cotangents overflowed in the VJP sweep: still cut
+                # scale_cotangents: the sweep's largest exponent, and the envs whose exponent ever left 0
+                "cotangent_exp_max": int(E) if E is not None else 0,
+                "scaled_envs": int(stats[4]) if E is not None else 0}
 
     def train(self, steps: Optional[int] = None, verbose: bool = True):
         n = self.cfg.total_steps if steps is None else steps
@@ -548,6 +667,7 @@ class HumanoidAPGEnv:
 
     guarded_vjp = True
     native_apg = True  # APGTrainer's bookkeeping as native launches (apg_obs / apg_post / apg_obs_vjp)
+    native_vjp_scale = True  # the VJP kernel rescales exponent-carried cotangents itself (attach_vjp_scale)
 
     def __init__(self, env, vjp: str = "implicit"):
         from . import abi
@@ -591,6 +711,19 @@ class HumanoidAPGEnv:
 
     def step_vjp(self, act, gq, gv, grew, gaux, nonfinite=None):
         return self.env.step_vjp(act, gq, gv, grew, gaux, nonfinite)
+
+    def attach_vjp_scale(self, exp, threshold_log2: int):
+        """Exponent-carried cotangents in the guarded VJP launches (mjl_vjp_scale_attach): `exp` a
+        contiguous int32 CUDA tensor [num_envs], read and written by every later VJP call, true
+        cotangent = stored * 2^exp; None detaches. A host-side pointer set (fine under graph capture)."""
+        from ._lib import check, lib
+        if exp is not None and not (exp.is_cuda and exp.dtype == torch.int32 and exp.is_contiguous()
+                                    and exp.numel() == self.num_envs):
+            raise ValueError("exp must be a contiguous int32 CUDA tensor of num_envs elements")
+        check(lib().mjl_vjp_scale_attach(self.env.data.handle,
+                                         ctypes.c_void_p(exp.data_ptr() if exp is not None else None),
+                                         int(threshold_log2)))
+        self._vjp_exp = exp  # the library holds the address: keep the tensor alive while attached
 
     def enable_vjp_tape(self, slots: int):
         """Allocate `slots` VJP tape slots (MJL_OPT_VJP_TAPE; outside stream capture)."""

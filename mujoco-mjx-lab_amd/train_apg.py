@@ -61,6 +61,10 @@ def main():
     ap.add_argument("--rms-freeze-after", type=int, default=None,
                     help="no observation-statistics updates after this update (APGConfig.rms_freeze_after; not "
                          "the reference's rule, which updates them every 10 updates, train_apg.py:290-292)")
+    ap.add_argument("--scale-cotangents", action="store_true",
+                    help="carry a per-env power-of-two exponent beside the reverse sweep's cotangents, so envs whose "
+                         "chained step Jacobians leave fp32 range stay in the gradient (DESIGN.md 3b); off: the "
+                         "guard cuts them (reverse_nonfinite_envs)")
     a = ap.parse_args()
 
     cfg = APGConfig()
@@ -87,7 +91,8 @@ def main():
                       device=local, seed=cfg.seed * 7919 + rank)
     out = os.path.join(cfg.results_dir, time.strftime("%Y%m%d_%H%M%S") + "_apg") if rank == 0 else None
     vjp = a.vjp or ("unrolled" if a.solver == "cg" else "implicit")
-    tr = APGTrainer(cfg, HumanoidAPGEnv(env, vjp), device=f"cuda:{local}", dist=dist, out_dir=out)
+    tr = APGTrainer(cfg, HumanoidAPGEnv(env, vjp), device=f"cuda:{local}", dist=dist, out_dir=out,
+                    scale_cotangents=a.scale_cotangents)
     tr.train()
     if dist is not None:
         dist.destroy_process_group()
