@@ -159,6 +159,14 @@ INL unsigned wmax_u(unsigned u) {
   v = mx(v, dpp0<0x143, 0xC>(v));
   return __float_as_uint(rdlane(v, 63));
 }
+// Wave-uniform values as scalars. gfx950 has no scalar float ALU, so a test of a wave-uniform float is
+// a VALU compare whose result the compiler must take for a lane mask: a branch on it saves and
+// restores exec, branches on execz, merges masks and copies every live value across the join. uni()
+// hands the compiler the same predicate as a scalar condition (any lane = every lane when all lanes
+// hold the same value; all 64 lanes are active wherever the solver calls it), uni_int() a uniform
+// integer that came through a vector load (LDS) as an SGPR.
+INL bool uni(bool c) { return __ballot(c) != 0ull; }
+INL int uni_int(int x) { return __builtin_amdgcn_readfirstlane(x); }
 INL unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
 // The lane index through an opaque move: lane masks compared against it are computed where they
 // are used. Against a plain lane index the compiler hoists a loop's 27 mask compares out of the
@@ -1482,12 +1490,20 @@ template <class D, class RowF> INL float jrow(RowF* J, LDSA float* v, int r) {  
   return rowdot<D::LD>(J + r * D::LD, v);
 }
 
+// Whether every row has its own lane (nefc <= 64): known at compile time for the LDS rows (build_rows
+// admits at most CAP of them), one scalar test for the global slab. The solver's passes over rows
+// 64.. are compiled away / branched around on it.
+template <class D, bool G> INL bool rows_fit_wave(int nefc) {
+  if constexpr (!G && D::CAP <= 64) return true;
+  return nefc <= 64;
+}
+
 // forces, cost, qfrc_constraint and gradient at the current qacc / Ma / jar; returns the cost and
 // |grad|^2 (two wave sums issued together)
 template <class D, bool G> INL float solver_update(MP m_, LDSA WS<D>* W, Rows<G> R, int lane, float& gsq) {
   MP m = uniform_ptr(m_);
   constexpr int LD = D::LD;
-  const int nv = m->nv, nefc = W->nefc;
+  const int nv = m->nv, nefc = uni_int(W->nefc);
   // clamped indices throughout: each group of loads issues before its first use
   float c = 0.f;
   {
@@ -1497,7 +1513,7 @@ template <class D, bool G> INL float solver_update(MP m_, LDSA WS<D>* W, Rows<G>
     if (lane < nefc) R.force[lane] = act ? -dr * j : 0.f;
     c = act ? 0.5f * dr * j * j : 0.f;
   }
-  for (int r = lane + 64; r < nefc; r += 64) {
+  if (!rows_fit_wave<D, G>(nefc)) for (int r = lane + 64; r < nefc; r += 64) {
     float j = R.jar[r];
     float f = j < 0.f ? -R.D[r] * j : 0.f;
     R.force[r] = f;
@@ -1536,7 +1552,7 @@ template <class D, bool G> INL float solver_update(MP m_, LDSA WS<D>* W, Rows<G>
 template <class D, bool G> INL f32x16 solver_hessian_acc(MP m_, LDSA WS<D>* W, Rows<G> R, int lane) {
   MP m = uniform_ptr(m_);
   constexpr int LD = D::LD;
-  const int nv = m->nv, nefc = W->nefc;
+  const int nv = m->nv, nefc = uni_int(W->nefc);
   const int col = lane & 31, kh = lane >> 5;
   f32x16 acc;
 #pragma unroll
@@ -1545,7 +1561,8 @@ template <class D, bool G> INL f32x16 solver_hessian_acc(MP m_, LDSA WS<D>* W, R
   // only active rows (jar < 0) contribute: take them in order from each 64-row ballot, 8 rows per
   // trip (uniform row indices from s_ff1), loads of the trip first, then one MFMA per row pair
   for (int base = 0; base < nefc; base += 64) {
-    unsigned long long am = __ballot(base + lane < nefc && R.jar[base + lane] < 0.f);
+    const int rb = base + lane < nefc ? base + lane : 0;  // clamped: no branch around the load
+    unsigned long long am = __ballot(base + lane < nefc & R.jar[rb] < 0.f);
     while (am) {
       int rr[8];
 #pragma unroll
@@ -1609,10 +1626,15 @@ template <class D, bool G> INL void solver_hessian(MP m_, LDSA WS<D>* W, Rows<G>
 // Costs are relative to the Gauss term at alpha = 0 (common to every point, so comparisons hold).
 // TP: tape hooks (NoTape in the primal kernels; the APG VJP's unrolled mode records every Newton
 // point's parent active set and the accepted alpha's weights over them, adjoint.hip SolveTape).
-template <class D, bool G, class TP> INL float solver_linesearch(MP m_, LDSA WS<D>* W, Rows<G> R, int lane, TP& tp) {
+// WIDE: rows 64.. exist (the second register slot for rows 64..127 and the loops over rows 128..);
+// the narrow variant compiles them away. A zero slot adds nothing to any sum, so both variants give
+// an env of at most 64 rows the same bits.
+// Every decision here is on wave-uniform values (wave sums and model constants) and is taken as a
+// scalar branch (uni) or a select, so the three-point loop's body is straight-line code.
+template <class D, bool G, bool WIDE, class TP> INL float solver_linesearch(MP m_, LDSA WS<D>* W, Rows<G> R, int lane, TP& tp) {
   MP m = uniform_ptr(m_);
   TSTART(tl);
-  const int nv = m->nv, nefc = W->nefc;
+  const int nv = m->nv, nefc = uni_int(W->nefc);
   // M s, J s (the first 128 rows' J s, jar and D stay in registers across the iterations)
   // (clamped row indices: the M s and J s loads issue together, no branch between them)
   const int mi = lane < nv ? lane : 0, ri = lane < nefc ? lane : 0;
@@ -1626,21 +1648,25 @@ template <class D, bool G, class TP> INL float solver_linesearch(MP m_, LDSA WS<
     const float ja = R.jar[ri], dd = R.D[ri];
     if (lane < nefc) { jv0 = jva; ja0 = ja; dd0 = dd; R.Jv[lane] = jv0; }
   }
-  if (lane + 64 < nefc) {
-    jv1 = jrow<D>(R.J, W->search, lane + 64); ja1 = R.jar[lane + 64]; dd1 = R.D[lane + 64]; R.Jv[lane + 64] = jv1;
+  if constexpr (WIDE) {
+    if (lane + 64 < nefc) {
+      jv1 = jrow<D>(R.J, W->search, lane + 64); ja1 = R.jar[lane + 64]; dd1 = R.D[lane + 64]; R.Jv[lane + 64] = jv1;
+    }
+    for (int r = lane + 128; r < nefc; r += 64) R.Jv[r] = jrow<D>(R.J, W->search, r);
   }
-  for (int r = lane + 128; r < nefc; r += 64) R.Jv[r] = jrow<D>(R.J, W->search, r);
   // (Mv / Jv entries are read back only by the lanes that wrote them: no barrier in the primal)
   if constexpr (TP::on) SYNC();
   if constexpr (TP::on) tp.ls_begin(W, lane);
   TACC(28, tl, lane);
   // the step qacc += a s, Ma += a M s, jar += a J s from the registers the search already holds
   auto apply = [&](float alpha) -> float {
-    if (alpha != 0.f) {
+    if (uni(alpha != 0.f)) {
       if (lane < nv) { W->qacc[lane] += alpha * sv; W->Ma[lane] += alpha * mvl; }
       if (lane < nefc) R.jar[lane] = ja0 + alpha * jv0;
-      if (lane + 64 < nefc) R.jar[lane + 64] = ja1 + alpha * jv1;
-      for (int r = lane + 128; r < nefc; r += 64) R.jar[r] += alpha * R.Jv[r];
+      if constexpr (WIDE) {
+        if (lane + 64 < nefc) R.jar[lane + 64] = ja1 + alpha * jv1;
+        for (int r = lane + 128; r < nefc; r += 64) R.jar[r] += alpha * R.Jv[r];
+      }
     }
     return alpha;
   };
@@ -1661,8 +1687,10 @@ template <class D, bool G, class TP> INL float solver_linesearch(MP m_, LDSA WS<
       }
     };
     row(ja0, jv0, dd0);
-    row(ja1, jv1, dd1);
-    for (int r = lane + 128; r < nefc; r += 64) row(R.jar[r], R.Jv[r], R.D[r]);
+    if constexpr (WIDE) {
+      row(ja1, jv1, dd1);
+      for (int r = lane + 128; r < nefc; r += 64) row(R.jar[r], R.Jv[r], R.D[r]);
+    }
   };
   float c1 = 0.f, c2 = 0.f;
   auto fin = [&](auto Kc, auto COSTc, const float* al, const float* dp, const float* hp, float* o0, float* o1) {
@@ -1709,8 +1737,11 @@ template <class D, bool G, class TP> INL float solver_linesearch(MP m_, LDSA WS<
   // exact segment: if no row changes activity between 0 and q, f' is linear there and q is its
   // root, the minimiser MJX's iterations then only jitter around in rounding noise
   {
-    bool same = ((ja0 < 0.f) == (ja0 + a1[0] * jv0 < 0.f)) && ((ja1 < 0.f) == (ja1 + a1[0] * jv1 < 0.f));
-    for (int r = lane + 128; r < nefc; r += 64) same &= (R.jar[r] < 0.f) == (R.jar[r] + a1[0] * R.Jv[r] < 0.f);
+    bool same = (ja0 < 0.f) == (ja0 + a1[0] * jv0 < 0.f);
+    if constexpr (WIDE) {
+      same &= (ja1 < 0.f) == (ja1 + a1[0] * jv1 < 0.f);
+      for (int r = lane + 128; r < nefc; r += 64) same &= (R.jar[r] < 0.f) == (R.jar[r] + a1[0] * R.Jv[r] < 0.f);
+    }
     if (__ballot(!same) == 0ull) {
       TCOUNT(15, 1, lane);
       if constexpr (TP::on) tp.ls_end(a1[0], rec_q, lane);
@@ -1720,10 +1751,10 @@ template <class D, bool G, class TP> INL float solver_linesearch(MP m_, LDSA WS<
   eval(I1{}, TF{}, a1, qd0, qd1);
   TACC(30, tl, lane);
   // lo = whichever of p0, q has the smaller f'
-  float loa, lod0, lod1, hia, hid0, hid1;
-  if (qd0[0] < p0d0[0]) { loa = a1[0]; lod0 = qd0[0]; lod1 = qd1[0]; hia = 0.f; hid0 = p0d0[0]; hid1 = p0d1[0]; }
-  else { loa = 0.f; lod0 = p0d0[0]; lod1 = p0d1[0]; hia = a1[0]; hid0 = qd0[0]; hid1 = qd1[0]; }
-  if constexpr (TP::on) { if (qd0[0] < p0d0[0]) rec_lo = rec_q; else rec_hi = rec_q; }
+  const bool qlo = qd0[0] < p0d0[0];
+  float loa = qlo ? a1[0] : 0.f, lod0 = qlo ? qd0[0] : p0d0[0], lod1 = qlo ? qd1[0] : p0d1[0];
+  float hia = qlo ? 0.f : a1[0], hid0 = qlo ? p0d0[0] : qd0[0], hid1 = qlo ? p0d1[0] : qd1[0];
+  if constexpr (TP::on) { rec_lo = qlo ? rec_q : rec_lo; rec_hi = qlo ? rec_hi : rec_q; }
   // MJX's gtol (tolerance * ls_tolerance * |search|) sits below the fp32 resolution of f', where
   // MJX's fp32 iterations only shuffle lo / hi within rounding noise until ls_iterations: an end
   // also counts as converged once |f'| is within kNoise of the magnitude of the terms summed into
@@ -1735,8 +1766,8 @@ template <class D, bool G, class TP> INL float solver_linesearch(MP m_, LDSA WS<
   float lot = tol(loa, lod0, lod1), hit = tol(hia, hid0, hid1);
   const int lsit = m->ls_iterations;
   for (int it = 0; it < lsit; it++) {
-    if ((lod0 < 0.f && lod0 > -lot) || (hid0 > 0.f && hid0 < hit)) break;
-    if (fabsf(hia - loa) <= 1e-6f * fmaxf(fabsf(loa), fabsf(hia))) break;
+    if (uni((lod0 < 0.f && lod0 > -lot) || (hid0 > 0.f && hid0 < hit))) break;
+    if (uni(fabsf(hia - loa) <= 1e-6f * fmaxf(fabsf(loa), fabsf(hia)))) break;
     float al[3] = {loa - lod0 * __builtin_amdgcn_rcpf(lod1), hia - hid0 * __builtin_amdgcn_rcpf(hid1), 0.5f * (loa + hia)};
     float rc[3] = {0.f, 0.f, 0.f};
     if constexpr (TP::on) {
@@ -1746,16 +1777,21 @@ template <class D, bool G, class TP> INL float solver_linesearch(MP m_, LDSA WS<
     }
     float d0[3], d1[3];
     eval(I3{}, TF{}, al, d0, d1);
-    bool s1 = lod0 > 0.f || lod0 < d0[0];
-    if (s1) { loa = al[0]; lod0 = d0[0]; lod1 = d1[0]; if constexpr (TP::on) rec_lo = rc[0]; }
-    bool s2 = d0[2] < 0.f && lod0 < d0[2];
-    if (s2) { loa = al[2]; lod0 = d0[2]; lod1 = d1[2]; if constexpr (TP::on) rec_lo = rc[2]; }
-    bool s3 = hid0 < 0.f || hid0 > d0[1];
-    if (s3) { hia = al[1]; hid0 = d0[1]; hid1 = d1[1]; if constexpr (TP::on) rec_hi = rc[1]; }
-    bool s4 = d0[2] > 0.f && hid0 > d0[2];
-    if (s4) { hia = al[2]; hid0 = d0[2]; hid1 = d1[2]; if constexpr (TP::on) rec_hi = rc[2]; }
+    // the swap rules in MJX's order, as selects (s2 / s4 test the end s1 / s3 may have just moved)
+    const bool s1 = lod0 > 0.f || lod0 < d0[0];
+    loa = s1 ? al[0] : loa; lod0 = s1 ? d0[0] : lod0; lod1 = s1 ? d1[0] : lod1;
+    if constexpr (TP::on) rec_lo = s1 ? rc[0] : rec_lo;
+    const bool s2 = d0[2] < 0.f && lod0 < d0[2];
+    loa = s2 ? al[2] : loa; lod0 = s2 ? d0[2] : lod0; lod1 = s2 ? d1[2] : lod1;
+    if constexpr (TP::on) rec_lo = s2 ? rc[2] : rec_lo;
+    const bool s3 = hid0 < 0.f || hid0 > d0[1];
+    hia = s3 ? al[1] : hia; hid0 = s3 ? d0[1] : hid0; hid1 = s3 ? d1[1] : hid1;
+    if constexpr (TP::on) rec_hi = s3 ? rc[1] : rec_hi;
+    const bool s4 = d0[2] > 0.f && hid0 > d0[2];
+    hia = s4 ? al[2] : hia; hid0 = s4 ? d0[2] : hid0; hid1 = s4 ? d1[2] : hid1;
+    if constexpr (TP::on) rec_hi = s4 ? rc[2] : rec_hi;
     TCOUNT(14, 1, lane);
-    if (!(s1 || s2 || s3 || s4)) break;
+    if (!uni(s1 || s2 || s3 || s4)) break;
     lot = tol(loa, lod0, lod1);
     hit = tol(hia, hid0, hid1);
   }
@@ -1763,7 +1799,7 @@ template <class D, bool G, class TP> INL float solver_linesearch(MP m_, LDSA WS<
   float ac[3] = {0.f, loa, hia}, cost[3];
   TACC(31, tl, lane);
   eval(I3{}, TT{}, ac, cost, nullptr);
-  const bool improved = cost[1] < cost[0] || cost[2] < cost[0];
+  const bool improved = uni(cost[1] < cost[0] || cost[2] < cost[0]);
   const float alpha = cost[1] < cost[2] ? loa : hia;
   if constexpr (TP::on) tp.ls_end(improved ? alpha : 0.f, improved ? (cost[1] < cost[2] ? rec_lo : rec_hi) : 0.f, lane);
   return apply(improved ? alpha : 0.f);
@@ -1777,8 +1813,9 @@ struct NoTape {
 template <class D, bool G, class TP> PHASE void solver_t(MP m_, LDSA WS<D>* W, Rows<G> R, int lane, TP& tp) {
   MP m = uniform_ptr(m_);
   constexpr int LD = D::LD;
-  const int nv = m->nv, nefc = W->nefc;
+  const int nv = m->nv, nefc = uni_int(W->nefc);
   const bool newton = m->solver == MJL_SOLVER_NEWTON;
+  const bool narrow = rows_fit_wave<D, G>(nefc);  // no rows 64..: their passes are skipped
   if (nefc == 0) {
     if (lane < LD) { W->qacc[lane] = W->qacc_ws[lane] = W->qacc_smooth[lane]; W->frc_con[lane] = 0.f; }
     if (lane == 0) { W->niter = 0; W->sc[SC_NACT] = 0.f; }
@@ -1802,18 +1839,18 @@ template <class D, bool G, class TP> PHASE void solver_t(MP m_, LDSA WS<D>* W, R
     const float g = lane < nv ? 0.5f * (mq[w] - fs) * (qc[w][mi] - qs) : 0.f;
     const float j = jq[w] - ar;
     float c = (lane < nefc && j < 0.f) ? 0.5f * dr * j * j : 0.f;
-    for (int r = lane + 64; r < nefc; r += 64) {
+    if (!narrow) for (int r = lane + 64; r < nefc; r += 64) {
       float jr = jrow<D>(R.J, qc[w], r) - R.aref[r];
       if (jr < 0.f) c += 0.5f * R.D[r] * jr * jr;
     }
     cost2[w] = wsum(g + c);
   }
-  const int wsel = cost2[0] < cost2[1] ? 0 : 1;
+  const int wsel = uni(cost2[0] < cost2[1]) ? 0 : 1;
   LDSA float* q0 = qc[wsel];
   if (lane < LD) W->qacc[lane] = q0[lane];
   if (lane < nv) W->Ma[lane] = mq[wsel];
   if (lane < nefc) R.jar[lane] = jq[wsel] - ar;
-  for (int r = lane + 64; r < nefc; r += 64) R.jar[r] = jrow<D>(R.J, q0, r) - R.aref[r];
+  if (!narrow) for (int r = lane + 64; r < nefc; r += 64) R.jar[r] = jrow<D>(R.J, q0, r) - R.aref[r];
   // (qacc, Ma and jar entries are read next by the lanes that wrote them: no barrier in the primal)
   if constexpr (TP::on) SYNC();
   if constexpr (TP::on) tp.warm(wsel, lane);
@@ -1828,20 +1865,31 @@ template <class D, bool G, class TP> PHASE void solver_t(MP m_, LDSA WS<D>* W, R
   int iter = 0;
   const int maxit = m->iterations;
   const bool exact_exit = newton && nefc <= 256;
-  unsigned long long hm[4] = {0ull, 0ull, 0ull, 0ull};
+  constexpr int NM = (!G && D::CAP <= 64) ? 1 : 4;  // 64-row masks an env can have
+  unsigned long long hm[NM] = {};
   int nhess = 0, nact = 0;  // Hessians built, active rows summed over them (bench FLOP model)
   auto active_masks = [&](unsigned long long* out) {
+    out[0] = __ballot(lane < nefc & R.jar[ri] < 0.f);  // (clamped index: no branch around the load)
 #pragma unroll
-    for (int c = 0; c < 4; c++) {
+    for (int c = 1; c < NM; c++) {
       int r = lane + 64 * c;
-      out[c] = __ballot(r < nefc && R.jar[r] < 0.f);
+      out[c] = narrow ? 0ull : __ballot(r < nefc && R.jar[r] < 0.f);
     }
   };
   for (bool first = true;; first = false) {
     if (!first) {
-      float alpha = solver_linesearch<D, G>(m, W, R, lane, tp);
+      float alpha;
+      if constexpr (!G && D::CAP <= 64) {
+        alpha = solver_linesearch<D, G, false>(m, W, R, lane, tp);
+      } else {  // one scalar branch per line search
+        if (narrow) alpha = solver_linesearch<D, G, false>(m, W, R, lane, tp);
+        else alpha = solver_linesearch<D, G, true>(m, W, R, lane, tp);
+      }
+      // (counted here, once for both ways on: counted on the no-improvement exit alone, the counter
+      // joins a lane-divergent branch below with two values and the compiler keeps it per lane)
+      iter++;
 #ifndef MJL_DIAG_FIXIT
-      if (!(alpha != 0.f)) { iter++; break; }  // no improvement: MJX's next cond stops (also on NaN)
+      if (!uni(alpha != 0.f)) break;  // no improvement: MJX's next cond stops (also on NaN)
 #endif
       // (the line search applied the step to qacc, Ma and jar, each entry by the lane that reads it
       // next, so the primal needs no barrier here; the tape's hooks read across lanes)
@@ -1854,24 +1902,25 @@ template <class D, bool G, class TP> PHASE void solver_t(MP m_, LDSA WS<D>* W, R
     if constexpr (TP::on) tp.update(W, R, lane);
     if (first && maxit != 1) {  // MJX cond before the first body (iterations == 1 runs one body)
 #ifndef MJL_DIAG_FIXIT
-      if (maxit <= 0 || scale * sqrtf(gsq) < m->tolerance) break;
+      if (maxit <= 0 || uni(scale * sqrtf(gsq) < m->tolerance)) break;
 #endif
     }
     if (!first) {
-      iter++;
       float gnorm = scale * sqrtf(gsq);
       float improvement = scale * (oldcost - cost);
 #ifdef MJL_DIAG_FIXIT  // diagnostic: exactly `iterations` iterations (cost attribution by knockouts)
       if (iter >= maxit) break;
       (void)gnorm; (void)improvement;
 #else
-      if (improvement < m->tolerance || gnorm < m->tolerance || iter >= maxit) break;
+      if (uni(improvement < m->tolerance || gnorm < m->tolerance) || uni_int(iter) >= maxit) break;
 #endif
       if (exact_exit) {
-        unsigned long long am[4];
+        unsigned long long am[NM], differ = 0ull;
         active_masks(am);
+#pragma unroll
+        for (int c = 0; c < NM; c++) differ |= am[c] ^ hm[c];
 #ifndef MJL_DIAG_FIXIT
-        if (am[0] == hm[0] && am[1] == hm[1] && am[2] == hm[2] && am[3] == hm[3]) break;
+        if (uni(differ == 0ull)) break;
 #endif
       }
     }
@@ -1879,7 +1928,8 @@ template <class D, bool G, class TP> PHASE void solver_t(MP m_, LDSA WS<D>* W, R
     if (newton) {
       if (exact_exit) {
         active_masks(hm);
-        nact += __popcll(hm[0]) + __popcll(hm[1]) + __popcll(hm[2]) + __popcll(hm[3]);
+#pragma unroll
+        for (int c = 0; c < NM; c++) nact += __popcll(hm[c]);
         nhess++;
       }
       float x;
