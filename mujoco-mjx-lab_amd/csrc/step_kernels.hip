@@ -1498,30 +1498,71 @@ template <class D, bool G> INL bool rows_fit_wave(int nefc) {
   return nefc <= 64;
 }
 
-// forces, cost, qfrc_constraint and gradient at the current qacc / Ma / jar; returns the cost and
-// |grad|^2 (two wave sums issued together)
-template <class D, bool G> INL float solver_update(MP m_, LDSA WS<D>* W, Rows<G> R, int lane, float& gsq) {
+// An active set (row < nefc and jar < 0) as 64-row masks: rows 0..255, all an env with the exact exit
+// can have; one word where the rows are the LDS rows (kMaskWords). Named words, selected by scalar
+// compares: an indexed array would live in scratch.
+template <class D, bool G> constexpr int kMaskWords = (!G && D::CAP <= 64) ? 1 : 4;
+struct ActiveSet {
+  unsigned long long w0 = 0ull, w1 = 0ull, w2 = 0ull, w3 = 0ull;
+  INL unsigned long long word(int w) const { return w == 0 ? w0 : w == 1 ? w1 : w == 2 ? w2 : w3; }
+  INL unsigned long long differ(const ActiveSet& o) const { return (w0 ^ o.w0) | (w1 ^ o.w1) | (w2 ^ o.w2) | (w3 ^ o.w3); }
+  INL int count() const { return __popcll(w0) + __popcll(w1) + __popcll(w2) + __popcll(w3); }
+};
+
+// What a lane holds of the current point, in registers from the step's application (or the warm
+// start) to the Hessian: its rows `lane` and `lane + 64` (jar, D; slot 1 is zero where absent or the
+// env is narrow) and its dof's qacc and Ma (dof 0 for lanes past nv). LDS holds the same values
+// (sensors, the tape's hooks and the next iteration's row dots read them there).
+struct IterRegs {
+  float jar0, jar1, d0, d1, qacc, ma;
+};
+
+// forces, cost, qfrc_constraint and gradient at the current point x (qacc / Ma / jar); returns the
+// cost and |grad|^2 (two wave sums issued together), and the point's active set (row < nefc and
+// jar < 0) in am: the one derivation per iteration, shared by the forces, the exact-exit test and
+// the Hessian's row selection
+template <class D, bool G>
+INL float solver_update(MP m_, LDSA WS<D>* W, Rows<G> R, int lane, const IterRegs& x, ActiveSet& am, float& gsq) {
   MP m = uniform_ptr(m_);
   constexpr int LD = D::LD;
+  constexpr int NM = kMaskWords<D, G>;
   const int nv = m->nv, nefc = uni_int(W->nefc);
-  // clamped indices throughout: each group of loads issues before its first use
+  // (issued first, used after the J'f loop: no wait of their own)
+  const int mi = lane < nv ? lane : 0;
+  const float fs = W->frc_smooth[mi], qsm = W->qacc_smooth[mi];
   float c = 0.f;
   {
-    const int ri = lane < nefc ? lane : 0;
-    const float j = R.jar[ri], dr = R.D[ri];
+    const float j = x.jar0, dr = x.d0;
     const bool act = lane < nefc && j < 0.f;
+    am = ActiveSet();
+    am.w0 = __ballot(act);
     if (lane < nefc) R.force[lane] = act ? -dr * j : 0.f;
     c = act ? 0.5f * dr * j * j : 0.f;
   }
-  if (!rows_fit_wave<D, G>(nefc)) for (int r = lane + 64; r < nefc; r += 64) {
-    float j = R.jar[r];
-    float f = j < 0.f ? -R.D[r] * j : 0.f;
-    R.force[r] = f;
-    if (j < 0.f) c += 0.5f * R.D[r] * j * j;
+  if (!rows_fit_wave<D, G>(nefc)) {
+    {  // rows 64..127 from the second register slot
+      const int r = lane + 64;
+      const float j = x.jar1, dr = x.d1;
+      const bool act = r < nefc && j < 0.f;
+      am.w1 = __ballot(act);
+      if (r < nefc) R.force[r] = act ? -dr * j : 0.f;
+      if (act) c += 0.5f * dr * j * j;
+    }
+    for (int r = lane + 128; r < nefc; r += 64) {
+      float j = R.jar[r];
+      float f = j < 0.f ? -R.D[r] * j : 0.f;
+      R.force[r] = f;
+      if (j < 0.f) c += 0.5f * R.D[r] * j * j;
+    }
+    if constexpr (NM > 2) {  // (clamped indices: no branch around the loads; each entry's reader wrote it)
+      const int r2 = lane + 128, r3 = lane + 192;
+      const float j2 = R.jar[r2 < nefc ? r2 : 0], j3 = R.jar[r3 < nefc ? r3 : 0];
+      am.w2 = __ballot(r2 < nefc & j2 < 0.f);
+      am.w3 = __ballot(r3 < nefc & j3 < 0.f);
+    }
   }
-  const int mi = lane < nv ? lane : 0;
-  const float ma = W->Ma[mi], fs = W->frc_smooth[mi], qa = W->qacc[mi], qsm = W->qacc_smooth[mi];
-  SYNC();
+  const float ma = x.ma, qa = x.qacc;
+  SYNC();  // force is read across lanes below
   const int d = lane & 31, h = lane >> 5;  // J' f : lane%32 = dof, lane/32 = row parity
   float s = 0.f;
   if (d < nv) {
@@ -1549,20 +1590,28 @@ template <class D, bool G> INL float solver_update(MP m_, LDSA WS<D>* W, Rows<G>
 // v_mfma_f32_32x32x2_f32 takes two constraint rows per instruction, lane l supplying
 // A[i][k] = D_r J[r][i] (active rows only) and B[k][j] = J[r][j] with i = j = l & 31, r = r0 + (l >> 5);
 // the 32x32 accumulator (nv <= 32) is H - M in the C layout row = (v&3) + 8(v>>2) + 4(l>>5), col = l&31.
-template <class D, bool G> INL f32x16 solver_hessian_acc(MP m_, LDSA WS<D>* W, Rows<G> R, int lane) {
+// am: the active set as 64-row masks (solver_update's), rows past 64 * kMaskWords from their jar.
+template <class D, bool G>
+INL f32x16 solver_hessian_acc(MP m_, LDSA WS<D>* W, Rows<G> R, int lane, const ActiveSet& as) {
   MP m = uniform_ptr(m_);
   constexpr int LD = D::LD;
+  constexpr int NM = kMaskWords<D, G>;
   const int nv = m->nv, nefc = uni_int(W->nefc);
   const int col = lane & 31, kh = lane >> 5;
   f32x16 acc;
 #pragma unroll
   for (int v = 0; v < 16; v++) acc[v] = 0.f;
 #ifndef MJL_HESS_DENSE
-  // only active rows (jar < 0) contribute: take them in order from each 64-row ballot, 8 rows per
+  // only active rows (jar < 0) contribute: take them in order from each 64-row mask, 8 rows per
   // trip (uniform row indices from s_ff1), loads of the trip first, then one MFMA per row pair
-  for (int base = 0; base < nefc; base += 64) {
-    const int rb = base + lane < nefc ? base + lane : 0;  // clamped: no branch around the load
-    unsigned long long am = __ballot(base + lane < nefc & R.jar[rb] < 0.f);
+  for (int base = 0, w = 0; base < nefc && (NM > 1 || base == 0); base += 64, w++) {  // (NM == 1: one trip)
+    unsigned long long am;
+    if (NM == 1 || w < NM) {
+      am = NM == 1 ? as.w0 : as.word(w);
+    } else {
+      const int rb = base + lane < nefc ? base + lane : 0;  // clamped: no branch around the load
+      am = __ballot(base + lane < nefc & R.jar[rb] < 0.f);
+    }
     while (am) {
       int rr[8];
 #pragma unroll
@@ -1605,17 +1654,35 @@ template <class D, bool G> INL f32x16 solver_hessian_acc(MP m_, LDSA WS<D>* W, R
   }
   return acc;
 }
-template <class D, bool G> INL void solver_hessian(MP m_, LDSA WS<D>* W, Rows<G> R, int lane) {
+// the active set of the jar in LDS (callers outside the Newton loop: the adjoint's Hessians)
+template <class D, bool G> INL ActiveSet solver_active_set(LDSA WS<D>* W, Rows<G> R, int lane) {
+  const int nefc = uni_int(W->nefc);
+  auto word = [&](int w) {  // clamped: no branch around the load
+    const int r = lane + 64 * w;
+    return __ballot(r < nefc & R.jar[r < nefc ? r : 0] < 0.f);
+  };
+  ActiveSet am;
+  am.w0 = word(0);
+  if constexpr (kMaskWords<D, G> > 1) { am.w1 = word(1); am.w2 = word(2); am.w3 = word(3); }
+  return am;
+}
+template <class D, bool G> INL f32x16 solver_hessian_acc(MP m_, LDSA WS<D>* W, Rows<G> R, int lane) {
+  return solver_hessian_acc<D, G>(m_, W, R, lane, solver_active_set<D, G>(W, R, lane));
+}
+template <class D, bool G> INL void solver_hessian(MP m_, LDSA WS<D>* W, Rows<G> R, int lane, const ActiveSet& am) {
   constexpr int LD = D::LD;
   const int nv = uniform_ptr(m_)->nv;
   const int col = lane & 31, kh = lane >> 5;
-  const f32x16 acc = solver_hessian_acc<D, G>(m_, W, R, lane);
+  const f32x16 acc = solver_hessian_acc<D, G>(m_, W, R, lane, am);
 #pragma unroll
   for (int v = 0; v < 16; v++) {
     const int row = (v & 3) + 8 * (v >> 2) + 4 * kh;
     if (row < nv && col < nv) W->H[row * LD + col] = W->M[row * LD + col] + acc[v];
   }
   SYNC();
+}
+template <class D, bool G> INL void solver_hessian(MP m_, LDSA WS<D>* W, Rows<G> R, int lane) {
+  solver_hessian<D, G>(m_, W, R, lane, solver_active_set<D, G>(W, R, lane));
 }
 
 // MJX's zoom line search along `search` (mujoco-mjx 3.3.6 solver.py _linesearch, restated in
@@ -1631,7 +1698,11 @@ template <class D, bool G> INL void solver_hessian(MP m_, LDSA WS<D>* W, Rows<G>
 // an env of at most 64 rows the same bits.
 // Every decision here is on wave-uniform values (wave sums and model constants) and is taken as a
 // scalar branch (uni) or a select, so the three-point loop's body is straight-line code.
-template <class D, bool G, bool WIDE, class TP> INL float solver_linesearch(MP m_, LDSA WS<D>* W, Rows<G> R, int lane, TP& tp) {
+// x (out): the lane's registers of the point the search ends at (IterRegs): the new point's where a
+// step is applied, the starting point's where alpha = 0. The old qacc loads with the first batch, so
+// solver_update reloads none of them and does not wait for jar / D before its forces.
+template <class D, bool G, bool WIDE, class TP>
+INL float solver_linesearch(MP m_, LDSA WS<D>* W, Rows<G> R, int lane, TP& tp, IterRegs& x) {
   MP m = uniform_ptr(m_);
   TSTART(tl);
   const int nv = m->nv, nefc = uni_int(W->nefc);
@@ -1641,7 +1712,8 @@ template <class D, bool G, bool WIDE, class TP> INL float solver_linesearch(MP m
   const float mva = mrow<D>(W, W->search, mi), jva = jrow<D>(R.J, W->search, ri);
   const float sv = (lane < nv) ? W->search[mi] : 0.f;
   const float mvl = (lane < nv) ? mva : 0.f;
-  const float c1p = sv * (W->Ma[mi] - W->frc_smooth[mi]), c2p = sv * mvl;
+  const float ma0 = W->Ma[mi], qa0 = W->qacc[mi];
+  const float c1p = sv * (ma0 - W->frc_smooth[mi]), c2p = sv * mvl;
   if (lane < nv) W->Mv[lane] = mvl;
   float jv0 = 0.f, ja0 = 0.f, dd0 = 0.f, jv1 = 0.f, ja1 = 0.f, dd1 = 0.f;
   {
@@ -1659,12 +1731,18 @@ template <class D, bool G, bool WIDE, class TP> INL float solver_linesearch(MP m
   if constexpr (TP::on) tp.ls_begin(W, lane);
   TACC(28, tl, lane);
   // the step qacc += a s, Ma += a M s, jar += a J s from the registers the search already holds
+  // (the new values stay in x for solver_update; the stores keep LDS equal to them)
   auto apply = [&](float alpha) -> float {
+    x.jar0 = ja0; x.jar1 = ja1; x.d0 = dd0; x.d1 = dd1; x.qacc = qa0; x.ma = ma0;
     if (uni(alpha != 0.f)) {
-      if (lane < nv) { W->qacc[lane] += alpha * sv; W->Ma[lane] += alpha * mvl; }
-      if (lane < nefc) R.jar[lane] = ja0 + alpha * jv0;
+      x.qacc = qa0 + alpha * sv;
+      x.ma = ma0 + alpha * mvl;
+      x.jar0 = ja0 + alpha * jv0;
+      if (lane < nv) { W->qacc[lane] = x.qacc; W->Ma[lane] = x.ma; }
+      if (lane < nefc) R.jar[lane] = x.jar0;
       if constexpr (WIDE) {
-        if (lane + 64 < nefc) R.jar[lane + 64] = ja1 + alpha * jv1;
+        x.jar1 = ja1 + alpha * jv1;
+        if (lane + 64 < nefc) R.jar[lane + 64] = x.jar1;
         for (int r = lane + 128; r < nefc; r += 64) R.jar[r] += alpha * R.Jv[r];
       }
     }
@@ -1829,14 +1907,14 @@ template <class D, bool G, class TP> PHASE void solver_t(MP m_, LDSA WS<D>* W, R
   // candidate's M q and J q - aref are kept as Ma and jar (the same values a recompute would give)
   const int mi = lane < nv ? lane : 0, ri = lane < nefc ? lane : 0;
   LDSA float* qc[2] = {W->qacc_ws, W->qacc_smooth};
-  float mq[2], jq[2];
+  float mq[2], jq[2], qv[2];
 #pragma unroll
-  for (int w = 0; w < 2; w++) { mq[w] = mrow<D>(W, qc[w], mi); jq[w] = jrow<D>(R.J, qc[w], ri); }
+  for (int w = 0; w < 2; w++) { mq[w] = mrow<D>(W, qc[w], mi); jq[w] = jrow<D>(R.J, qc[w], ri); qv[w] = qc[w][mi]; }
   const float fs = W->frc_smooth[mi], qs = W->qacc_smooth[mi], ar = R.aref[ri], dr = R.D[ri];
   float cost2[2];
 #pragma unroll
   for (int w = 0; w < 2; w++) {
-    const float g = lane < nv ? 0.5f * (mq[w] - fs) * (qc[w][mi] - qs) : 0.f;
+    const float g = lane < nv ? 0.5f * (mq[w] - fs) * (qv[w] - qs) : 0.f;
     const float j = jq[w] - ar;
     float c = (lane < nefc && j < 0.f) ? 0.5f * dr * j * j : 0.f;
     if (!narrow) for (int r = lane + 64; r < nefc; r += 64) {
@@ -1847,10 +1925,19 @@ template <class D, bool G, class TP> PHASE void solver_t(MP m_, LDSA WS<D>* W, R
   }
   const int wsel = uni(cost2[0] < cost2[1]) ? 0 : 1;
   LDSA float* q0 = qc[wsel];
+  // the chosen point's lane registers seed the first update the way a line search's step does later
+  IterRegs x = {jq[wsel] - ar, 0.f, dr, 0.f, qv[wsel], mq[wsel]};
   if (lane < LD) W->qacc[lane] = q0[lane];
-  if (lane < nv) W->Ma[lane] = mq[wsel];
-  if (lane < nefc) R.jar[lane] = jq[wsel] - ar;
-  if (!narrow) for (int r = lane + 64; r < nefc; r += 64) R.jar[r] = jrow<D>(R.J, q0, r) - R.aref[r];
+  if (lane < nv) W->Ma[lane] = x.ma;
+  if (lane < nefc) R.jar[lane] = x.jar0;
+  if (!narrow) {
+    if (lane + 64 < nefc) {
+      x.jar1 = jrow<D>(R.J, q0, lane + 64) - R.aref[lane + 64];
+      x.d1 = R.D[lane + 64];
+      R.jar[lane + 64] = x.jar1;
+    }
+    for (int r = lane + 128; r < nefc; r += 64) R.jar[r] = jrow<D>(R.J, q0, r) - R.aref[r];
+  }
   // (qacc, Ma and jar entries are read next by the lanes that wrote them: no barrier in the primal)
   if constexpr (TP::on) SYNC();
   if constexpr (TP::on) tp.warm(wsel, lane);
@@ -1865,25 +1952,16 @@ template <class D, bool G, class TP> PHASE void solver_t(MP m_, LDSA WS<D>* W, R
   int iter = 0;
   const int maxit = m->iterations;
   const bool exact_exit = newton && nefc <= 256;
-  constexpr int NM = (!G && D::CAP <= 64) ? 1 : 4;  // 64-row masks an env can have
-  unsigned long long hm[NM] = {};
+  ActiveSet hm, am;  // the active set the last Hessian was built from; the current point's
   int nhess = 0, nact = 0;  // Hessians built, active rows summed over them (bench FLOP model)
-  auto active_masks = [&](unsigned long long* out) {
-    out[0] = __ballot(lane < nefc & R.jar[ri] < 0.f);  // (clamped index: no branch around the load)
-#pragma unroll
-    for (int c = 1; c < NM; c++) {
-      int r = lane + 64 * c;
-      out[c] = narrow ? 0ull : __ballot(r < nefc && R.jar[r] < 0.f);
-    }
-  };
   for (bool first = true;; first = false) {
     if (!first) {
       float alpha;
       if constexpr (!G && D::CAP <= 64) {
-        alpha = solver_linesearch<D, G, false>(m, W, R, lane, tp);
+        alpha = solver_linesearch<D, G, false>(m, W, R, lane, tp, x);
       } else {  // one scalar branch per line search
-        if (narrow) alpha = solver_linesearch<D, G, false>(m, W, R, lane, tp);
-        else alpha = solver_linesearch<D, G, true>(m, W, R, lane, tp);
+        if (narrow) alpha = solver_linesearch<D, G, false>(m, W, R, lane, tp, x);
+        else alpha = solver_linesearch<D, G, true>(m, W, R, lane, tp, x);
       }
       // (counted here, once for both ways on: counted on the no-improvement exit alone, the counter
       // joins a lane-divergent branch below with two values and the compiler keeps it per lane)
@@ -1891,14 +1969,15 @@ template <class D, bool G, class TP> PHASE void solver_t(MP m_, LDSA WS<D>* W, R
 #ifndef MJL_DIAG_FIXIT
       if (!uni(alpha != 0.f)) break;  // no improvement: MJX's next cond stops (also on NaN)
 #endif
-      // (the line search applied the step to qacc, Ma and jar, each entry by the lane that reads it
-      // next, so the primal needs no barrier here; the tape's hooks read across lanes)
+      // (the line search applied the step to qacc, Ma and jar and left the new values in x, which the
+      // update takes: nothing is read back, so the primal needs no barrier here; the tape's hooks read
+      // LDS across lanes)
       if (!newton && lane < nv) { W->gradold[lane] = W->grad[lane]; W->Mgradold[lane] = W->Mgrad[lane]; }
       if constexpr (TP::on) SYNC();
       TACC(10, ts, lane);
     }
     float oldcost = cost, gsq;
-    cost = solver_update<D, G>(m, W, R, lane, gsq);
+    cost = solver_update<D, G>(m, W, R, lane, x, am, gsq);
     if constexpr (TP::on) tp.update(W, R, lane);
     if (first && maxit != 1) {  // MJX cond before the first body (iterations == 1 runs one body)
 #ifndef MJL_DIAG_FIXIT
@@ -1915,10 +1994,7 @@ template <class D, bool G, class TP> PHASE void solver_t(MP m_, LDSA WS<D>* W, R
       if (uni(improvement < m->tolerance || gnorm < m->tolerance) || uni_int(iter) >= maxit) break;
 #endif
       if (exact_exit) {
-        unsigned long long am[NM], differ = 0ull;
-        active_masks(am);
-#pragma unroll
-        for (int c = 0; c < NM; c++) differ |= am[c] ^ hm[c];
+        const unsigned long long differ = am.differ(hm);
 #ifndef MJL_DIAG_FIXIT
         if (uni(differ == 0ull)) break;
 #endif
@@ -1927,9 +2003,8 @@ template <class D, bool G, class TP> PHASE void solver_t(MP m_, LDSA WS<D>* W, R
     TACC(11, ts, lane);
     if (newton) {
       if (exact_exit) {
-        active_masks(hm);
-#pragma unroll
-        for (int c = 0; c < NM; c++) nact += __popcll(hm[c]);
+        hm = am;
+        nact += hm.count();
         nhess++;
       }
       float x;
@@ -1937,7 +2012,7 @@ template <class D, bool G, class TP> PHASE void solver_t(MP m_, LDSA WS<D>* W, R
 #ifdef MJL_DIAG_KO_HESS
         f32x16 acc = {};
 #else
-        const f32x16 acc = solver_hessian_acc<D, G>(m, W, R, lane);
+        const f32x16 acc = solver_hessian_acc<D, G>(m, W, R, lane, am);
 #endif
         TACC(12, ts, lane);
 #ifdef MJL_DIAG_KO_CHOL
@@ -1946,7 +2021,7 @@ template <class D, bool G, class TP> PHASE void solver_t(MP m_, LDSA WS<D>* W, R
         x = chol_aug_factor_solve<D, true>(W->M, W->H, W->invd, nv, W->grad, lane, acc);
 #endif
       } else {
-        solver_hessian<D, G>(m, W, R, lane);
+        solver_hessian<D, G>(m, W, R, lane, am);
         TACC(12, ts, lane);
         x = chol_factor_solve<D>(W->H, W->H, W->invd, nv, W->grad, lane);
       }
