@@ -203,6 +203,14 @@ struct SolveTape {
   GLBA float* acc;  // the reverse sweep's row accumulators (t + d.tape, or the env's own scratch)
   TapeDims d;
   int nup, nls, nsets, overflow;
+  // an empty tape for env `env`: the row accumulators in the env's unrolled scratch (unr: [nenv, dims.stride],
+  // null: no tape), the tape itself at slot_t (IN_SLOT: a VJP tape slot's) or at the head of that scratch
+  template <bool IN_SLOT> INL void attach(GLBA float* slot_t, float* unr, int env, const TapeDims& dims) {
+    t = unr ? (IN_SLOT ? slot_t : (GLBA float*)(unr + (size_t)env * dims.stride)) : nullptr;
+    acc = unr ? (GLBA float*)(unr + (size_t)env * dims.stride) + dims.tape : nullptr;
+    d = dims;
+    nup = nls = nsets = overflow = 0;
+  }
   INL GLBA float* upd(int k) const { return t + 4 + k * d.US; }
   INL GLBA float* ls(int k) const { return t + 4 + d.KU * d.US + k * d.LSS; }
   INL void put_mask(GLBA float* dst, int w, unsigned long long b, int lane) const {
@@ -1788,24 +1796,46 @@ template <class DM> struct WSAR {
   alignas(16) float invdc[LD];
   float ap[LD];
 };
-// slot layout of the A part: qpos0 [MAXQ], qvel0 [LD], aux [12], ap [LD], invdc [LD], Lc [NV * LD]
-template <class DM> __host__ __device__ constexpr int slot_a_floats() {
-  return MJL_MAXQ + DM::LD + 12 + 2 * DM::LD + DM::NV * DM::LD;
-}
+// The A part of a VJP tape slot, in floats from slot + s_a: the pre-step qpos [MAXQ] and qvel [LD], the
+// aux row (kAux floats reserved, MJL_AUX_DIM used), a' [LD], then the factor the reverse solve reads --
+// its inverse diagonal [LD] and rows [NV][LD]. The one description of the layout: the record kernels,
+// both replay loaders and the lean replay's in-slot reads all take their offsets from here.
+template <class DM> struct SlotA {
+  static constexpr int kAux = 12;
+  static_assert(MJL_AUX_DIM <= kAux, "the aux row outgrew its slot segment");
+  static constexpr int qpos0 = 0, qvel0 = qpos0 + MJL_MAXQ, aux = qvel0 + DM::LD, ap = aux + kAux, invdc = ap + DM::LD,
+                       Lc = invdc + DM::LD, floats = Lc + DM::NV * DM::LD;
+};
+template <class DM> __host__ __device__ constexpr int slot_a_floats() { return SlotA<DM>::floats; }
 template <class DM> __host__ __device__ constexpr int slot_w_floats() { return (int)(sizeof(WS<DM>) / 4); }
 
 // record / replay of the A part (lanes stride the arrays)
 template <class DM, class AT> INL void slot_a_io(GLBA float* sa, AT* A, LDSA float* aux, int lane, bool store) {
-  constexpr int LD = DM::LD, NV = DM::NV;
+  typedef SlotA<DM> S;
   auto mv = [&](LDSA float* l, GLBA float* g, int n) {
     for (int i = lane; i < n; i += 64) { if (store) g[i] = l[i]; else l[i] = g[i]; }
   };
-  mv((LDSA float*)A->qpos0, sa, MJL_MAXQ);
-  mv((LDSA float*)A->qvel0, sa + MJL_MAXQ, LD);
-  mv(aux, sa + MJL_MAXQ + LD, MJL_AUX_DIM);
-  mv((LDSA float*)A->ap, sa + MJL_MAXQ + LD + 12, LD);
-  mv((LDSA float*)A->invdc, sa + MJL_MAXQ + 2 * LD + 12, LD);
-  mv((LDSA float*)A->Lc, sa + MJL_MAXQ + 3 * LD + 12, NV * LD);
+  mv((LDSA float*)A->qpos0, sa + S::qpos0, MJL_MAXQ);
+  mv((LDSA float*)A->qvel0, sa + S::qvel0, DM::LD);
+  mv(aux, sa + S::aux, MJL_AUX_DIM);
+  mv((LDSA float*)A->ap, sa + S::ap, DM::LD);
+  mv((LDSA float*)A->invdc, sa + S::invdc, DM::LD);
+  mv((LDSA float*)A->Lc, sa + S::Lc, DM::NV * DM::LD);
+}
+
+// element i of the A part (value x) into its LDS home, for the segments below END (SlotA::floats, or
+// SlotA::invdc where the factor stays in the slot); the aux segment's padding and i >= END go nowhere
+template <class DM, int END, class AT> INL void slot_a_put(AT* A, LDSA float* aux, int i, float x) {
+  typedef SlotA<DM> S;
+  static_assert(END == S::floats || END == S::invdc, "whole A part, or up to a'");
+  if (i < S::qvel0) ((LDSA float*)A->qpos0)[i] = x;
+  else if (i < S::aux) ((LDSA float*)A->qvel0)[i - S::qvel0] = x;
+  else if (i < S::ap) { if (i - S::aux < MJL_AUX_DIM) aux[i - S::aux] = x; }
+  else if (i < S::invdc) ((LDSA float*)A->ap)[i - S::ap] = x;
+  else if constexpr (END > S::invdc) {
+    if (i < S::Lc) ((LDSA float*)A->invdc)[i - S::invdc] = x;
+    else if (i < S::floats) ((LDSA float*)A->Lc)[i - S::Lc] = x;
+  }
 }
 
 // replay's load of a tape slot into LDS: every global load of the workspace (b128) and of the A part
@@ -1813,10 +1843,8 @@ template <class DM, class AT> INL void slot_a_io(GLBA float* sa, AT* A, LDSA flo
 // own load: ~28 dependent HBM round trips per replayed step)
 template <class DM, class AT> INL void slot_replay_load(GLBA const float* sw, GLBA const float* sa, LDSA WS<DM>* W,
                                                       AT* A, LDSA float* aux, int lane) {
-  constexpr int LD = DM::LD, NV = DM::NV;
   constexpr int NW = (int)(sizeof(WS<DM>) / 16), QW = (NW + 63) / 64;
-  constexpr int NA = slot_a_floats<DM>(), QA = (NA + 63) / 64;
-  constexpr int O1 = MJL_MAXQ, O2 = O1 + LD, O3 = O2 + 12, O4 = O3 + LD, O5 = O4 + LD;  // A-part segments
+  constexpr int NA = SlotA<DM>::floats, QA = (NA + 63) / 64;
   f32x4 w[QW];
   float a[QA];
 #pragma unroll
@@ -1835,16 +1863,7 @@ template <class DM, class AT> INL void slot_replay_load(GLBA const float* sw, GL
     if (i < NW) ((LDSA f32x4*)W)[i] = w[q];
   }
 #pragma unroll
-  for (int q = 0; q < QA; q++) {
-    const int i = lane + 64 * q;
-    if (i < O1) ((LDSA float*)A->qpos0)[i] = a[q];
-    else if (i < O2) ((LDSA float*)A->qvel0)[i - O1] = a[q];
-    else if (i < O3) { if (i - O2 < MJL_AUX_DIM) aux[i - O2] = a[q]; }
-    else if (i < O4) ((LDSA float*)A->ap)[i - O3] = a[q];
-    else if (i < O5) ((LDSA float*)A->invdc)[i - O4] = a[q];
-    else if (i < NA) ((LDSA float*)A->Lc)[i - O5] = a[q];
-  }
-  (void)NV;
+  for (int q = 0; q < QA; q++) slot_a_put<DM, NA>(A, aux, lane + 64 * q, a[q]);
 }
 
 // the lean replay's slot load: the workspace image minus its matrix block (M, H, invd stay in the slot)
@@ -1853,15 +1872,13 @@ template <class DM, class AT> INL void slot_replay_load(GLBA const float* sw, GL
 // global_load_lds_dwordx4: 101.6 against 101.3 us per replay, not kept)
 template <class DM> INL void slot_replay_load_lean(GLBA const float* sw, GLBA const float* sa, LDSA WSB<DM>* W,
                                                    LDSA WSAL<DM>* A, LDSA float* aux, int lane) {
-  constexpr int LD = DM::LD;
   constexpr int MOFF = (int)(offsetof(WS<DM>, M) / 16), TOFF = (int)(offsetof(WS<DM>, frc_bias) / 16);
   constexpr int NB16 = (int)(sizeof(WSB<DM>) / 16), QW = (NB16 + 63) / 64;
   static_assert(offsetof(WSB<DM>, frc_bias) == offsetof(WS<DM>, M) && offsetof(WS<DM>, M) % 16 == 0 &&
                     offsetof(WS<DM>, frc_bias) % 16 == 0 &&
                     sizeof(WSB<DM>) + (offsetof(WS<DM>, frc_bias) - offsetof(WS<DM>, M)) == sizeof(WS<DM>),
                 "WSB is WS without its matrix block");
-  constexpr int O1 = MJL_MAXQ, O2 = O1 + LD, O3 = O2 + 12, O4 = O3 + LD;  // A-part segments up to a'
-  constexpr int QA = (O4 + 63) / 64;
+  constexpr int NA = SlotA<DM>::invdc, QA = (NA + 63) / 64;  // the A part up to a'
   f32x4 w[QW];
   float a[QA];
 #pragma unroll
@@ -1872,7 +1889,7 @@ template <class DM> INL void slot_replay_load_lean(GLBA const float* sw, GLBA co
 #pragma unroll
   for (int q = 0; q < QA; q++) {
     const int i = lane + 64 * q;
-    a[q] = i < O4 ? sa[i] : 0.f;
+    a[q] = i < NA ? sa[i] : 0.f;
   }
 #pragma unroll
   for (int q = 0; q < QW; q++) {
@@ -1880,13 +1897,7 @@ template <class DM> INL void slot_replay_load_lean(GLBA const float* sw, GLBA co
     if (i < NB16) ((LDSA f32x4*)W)[i] = w[q];
   }
 #pragma unroll
-  for (int q = 0; q < QA; q++) {
-    const int i = lane + 64 * q;
-    if (i < O1) ((LDSA float*)A->qpos0)[i] = a[q];
-    else if (i < O2) ((LDSA float*)A->qvel0)[i - O1] = a[q];
-    else if (i < O3) { if (i - O2 < MJL_AUX_DIM) aux[i - O2] = a[q]; }
-    else if (i < O4) ((LDSA float*)A->ap)[i - O3] = a[q];
-  }
+  for (int q = 0; q < QA; q++) slot_a_put<DM, NA>(A, aux, lane + 64 * q, a[q]);
 }
 
 // One wave per env: recompute the step from the batch state (not modified), then run the reverse
@@ -1937,6 +1948,8 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
     bool nz = (lane < nq && cq != 0.f) || (lane < nv && (cv != 0.f || cw != 0.f));
     if (ENV) nz = nz || (lane == 0 && cr != 0.f) || (lane < MJL_AUX_DIM && ca != 0.f);
     if (__ballot(nz) == 0ull) {
+      // (written out here and at the guard's exit below: as one helper it cost the lean replay 2 SGPR spills
+      // and 0.4 % of its time, profiles/r9/kernel_resource_usage.txt)
       if (lane < nq) V.o_qpos[(size_t)env * nq + lane] = 0.f;
       if (lane < nv) V.o_qvel[(size_t)env * nv + lane] = 0.f;
       if (lane < nu) V.o_ctrl[(size_t)env * nu + lane] = 0.f;
@@ -1962,20 +1975,19 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
   {  // zero the adjoint workspace and the LD-wide vectors of the forward one
     LDSA float* a = (LDSA float*)A;
     for (int i = lane; i < (int)(sizeof(AT) / 4); i += 64) a[i] = 0.f;
-    for (int i = lane; i < LD; i += 64) {
-      W->qvel[i] = 0.f; W->qacc_ws[i] = 0.f;
-      W->frc_bias[i] = W->frc_passive[i] = W->frc_act[i] = W->frc_smooth[i] = W->qacc_smooth[i] = 0.f;
-      W->qacc[i] = W->frc_con[i] = W->grad[i] = W->Mgrad[i] = W->search[i] = W->Ma[i] = W->Mv[i] = 0.f;
-      W->gradold[i] = W->Mgradold[i] = 0.f;
-    }
+    zero_ld_vectors<D>(W, lane);
   }
   SYNC();
   const bool unr = V.unr != nullptr;
   SolveTape tp;
-  tp.t = unr ? (TM ? slot + V.s_t : (GLBA float*)(V.unr + (size_t)env * V.td.stride)) : nullptr;
-  tp.acc = unr ? (GLBA float*)(V.unr + (size_t)env * V.td.stride) + V.td.tape : nullptr;
-  tp.d = V.td;
-  tp.nup = tp.nls = tp.nsets = tp.overflow = 0;
+  if constexpr (LEAN) {  // attach<true>, in place: through the helper the lean replay compiles to 2 more SGPR spills
+    tp.t = unr ? slot + V.s_t : nullptr;  // and measured 0.3 % slower (profiles/r9/kernel_resource_usage.txt)
+    tp.acc = unr ? (GLBA float*)(V.unr + (size_t)env * V.td.stride) + V.td.tape : nullptr;
+    tp.d = V.td;
+    tp.nup = tp.nls = tp.nsets = tp.overflow = 0;
+  } else {
+    tp.attach<TM != 0>(TM ? slot + V.s_t : nullptr, V.unr, env, V.td);
+  }
   Rows<true> R = global_rows<D>(TM ? (float*)(slot + V.s_r) : scr_env, P.gmax_efc, P.gmax_con);
   if constexpr (TM == 2) {  // replay: the forward's workspace, pre-step state and factors from the slot
     STAMP(0, lane);
@@ -1984,48 +1996,16 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
     SYNC();
     STAMP(1, lane);
   } else {
-  // every state load issues before the first wait (clamped lane indices, no branch per load)
-  // (a zero-size field clamps to index 0 and is not read)
-  const int iq = lane < nq ? lane : max(nq - 1, 0), iv = lane < nv ? lane : max(nv - 1, 0);
-  const int iu = lane < nu ? lane : max(nu - 1, 0);
-  const float q = nq > 0 ? S.qpos[(size_t)env * nq + iq] : 0.f;
-  const float v = nv > 0 ? S.qvel[(size_t)env * nv + iv] : 0.f;
-  const float w = nv > 0 ? S.qacc_warmstart[(size_t)env * nv + iv] : 0.f;
-  float c = nu > 0 ? (ENV ? V.act[(size_t)env * nu + iu] : S.ctrl[(size_t)env * nu + iu]) : 0.f;
-  const float t = S.time[env];
-  float ax = 0.f, sgn = 1.f;
-  int perm = iu;
-  if (ENV) {
-    const int ia = lane < MJL_AUX_DIM ? lane : MJL_AUX_DIM - 1;
-    ax = S.aux[(size_t)env * MJL_AUX_DIM + ia];
-    perm = nu > 0 ? P.env->act_perm[iu] : 0;
-    sgn = nu > 0 ? P.env->act_sign[iu] : 1.f;
+  {
+    const LaneState s0 = load_step_state<D, ENV, TM == 1>(m, S, P.env, ENV ? V.act : S.ctrl, W, aux, env, lane);
+    if (lane < nq) A->qpos0[lane] = s0.q;
+    if (lane < nv) A->qvel0[lane] = s0.v;
   }
-  if (lane < nq) { W->qpos[lane] = q; A->qpos0[lane] = q; }
-  if (lane < nv) { W->qvel[lane] = v; A->qvel0[lane] = v; W->qacc_ws[lane] = w; }
-  if (lane == 0) W->sc[SC_TIME] = t;
-  if (ENV) {  // flip + clip the action (envs.py:335-344): act[perm[j]] from lane perm[j]
-    if (lane < MJL_AUX_DIM) aux[lane] = ax;
-    const bool flip = rdlane(ax, 0) > 0.5f;
-    const float ap = __shfl(c, perm);
-    c = fminf(fmaxf(flip ? ap * sgn : c, -1.f), 1.f);
-    if (TM == 1 && lane == 0) W->sc[SC_FLIP] = ax;
-  }
-  if (lane < nu) W->ctrl[lane] = c;
   SYNC();
   // ---- forward (forward() + integrate(), rows in the env's global slab)
   STAMP(0, lane);
-  {
-    const KinPre kp = kin_prefetch(m, lane);
-    kinematics<D>(m, W, lane, kp);
-    com_pos_crb<D>(m, W, lane, kp);
-    velocity_stage<D>(m, W, lane, kp);
-  }
-  {
-    const float x = chol_factor_solve<D>(W->M, W->H, W->invd, nv, W->frc_smooth, lane);
-    if (lane < LD) W->qacc_smooth[lane] = (lane < nv) ? x : 0.f;
-    SYNC();
-  }
+  smooth_forward<D, false>(m, W, lane, kin_prefetch(m, lane));
+  SYNC();
   if constexpr (TM == 1) {  // unrolled CG: chol(M) -- the reverse sweep's preconditioner -- in the slot's Lc
     if (unr && m->solver != MJL_SOLVER_NEWTON) {
       for (int i = lane; i < D::NV * LD; i += 64) A->Lc[i] = W->H[i];
@@ -2056,18 +2036,9 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
       for (int i = lane; i < (int)(sizeof(WS<D>) / 16); i += 64) dst[i] = src[i];
       slot_a_io<D>(slot + V.s_a, A, aux, lane, true);
     }
-    float* obs = P.obs + (size_t)env * P.env->obs_dim;
-    env_post<D>(m, W, P.env, aux, obs, lane, false);
-    if (lane == 0) { P.rew[env] = W->sc[SC_REW]; P.term[env] = W->sc[SC_TERM]; P.trunc[env] = W->sc[SC_TRUNC]; }
+    env_step_outputs<D, false>(m, W, P, aux, env, lane, false);
     SYNC();
-    if (lane < nq) S.qpos[(size_t)env * nq + lane] = W->qpos[lane];
-    if (lane < nv) {
-      S.qvel[(size_t)env * nv + lane] = W->qvel[lane];
-      S.qacc_warmstart[(size_t)env * nv + lane] = W->qacc_ws[lane];
-    }
-    if (lane < nu) S.ctrl[(size_t)env * nu + lane] = W->ctrl[lane];
-    if (lane == 0) S.time[env] = W->sc[SC_TIME];
-    if (lane < MJL_AUX_DIM) S.aux[(size_t)env * MJL_AUX_DIM + lane] = aux[lane];
+    store_step_state<D, true>(S, W, aux, env, nq, nv, nu, lane);
     return;
   }
   }
@@ -2077,9 +2048,8 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
     if constexpr (LEAN) {
       GLBA const float* sw = slot + V.s_w;
       GLBA const float* sa = slot + V.s_a;
-      constexpr int O4 = MJL_MAXQ + 2 * LD + 12, O5 = O4 + LD;  // invdc, Lc in the A part (slot_a_io)
       return AdjMats<GLBA const float*>{sw + offsetof(WS<D>, M) / 4, sw + offsetof(WS<D>, H) / 4,
-                                        sw + offsetof(WS<D>, invd) / 4, sa + O5, sa + O4,
+                                        sw + offsetof(WS<D>, invd) / 4, sa + SlotA<D>::Lc, sa + SlotA<D>::invdc,
                                         (GLBA float*)(scr_adj + adj_scratch_floats(P.gmax_efc, P.gmax_con))};
     } else {
       return AdjMats<const LDSA float*>{W->M, W->H, W->invd, A->Lc, A->invdc, nullptr};
@@ -2282,16 +2252,7 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
 //  - the A part has no LDS copy: qpos0 / qvel0 / aux go to the slot from registers at the start,
 //    and a', the factor of Hc and its inverse diagonal are formed in the freed row area,
 // so the kernel's LDS is the env step's (8 waves per CU). Rows beyond the LDS capacity take the
-// global slab in the slot (record_rows_global), as vjp_kernel does for every env.
-template <class DL, int MW> NOINL void record_rows_global(MP m, LDSA WS<DL>* W, float* rows, int gmax_efc, int gmax_con,
-                                                          int lane) {
-  Rows<true> R = global_rows<DL>(rows, gmax_efc, gmax_con);
-  build_rows<DL, true>(m, W, R, lane);
-  solver<DL, true>(m, W, R, lane);
-  sensors<DL, true>(m, W, R, lane);
-  solver_hessian<DL, true>(m, W, R, lane);  // Hc at the converged active set, into H
-}
-
+// global slab in the slot (global_rows_path), as vjp_kernel does for every env.
 // UNR: the unrolled VJP's record (MJL_OPT_VJP_UNROLLED): the solve taped as vjp_kernel's record tapes it
 // (SolveTape into slot + s_t, row accumulators in V.unr), chol(M) in the A part for CG (the reverse sweep's
 // preconditioner) in place of the factor of Hc, which it does not use.
@@ -2317,65 +2278,27 @@ __global__ __launch_bounds__(64, 2) void vjp_record_kernel(KParams P, VjpArgs V)
   const StateBuf& S = P.s;
   GLBA float* slot = (GLBA float*)(V.slot + (size_t)env * (size_t)V.slot_stride);
   GLBA float* sa = slot + V.s_a;
-  constexpr int O1 = MJL_MAXQ, O2 = O1 + LD, O3 = O2 + 12;  // A part: qpos0, qvel0, aux, then a', 1/diag, Lc
+  typedef SlotA<DI> SA;
   constexpr int U0 = (int)(offsetof(WS<DI>, cinert) / 16), NI = (int)(sizeof(WS<DI>) / 16);
-  for (int i = lane; i < LD; i += 64) {  // the LD-wide vectors vjp_kernel zeroes
-    W->qvel[i] = 0.f; W->qacc_ws[i] = 0.f;
-    W->frc_bias[i] = W->frc_passive[i] = W->frc_act[i] = W->frc_smooth[i] = W->qacc_smooth[i] = 0.f;
-    W->qacc[i] = W->frc_con[i] = W->grad[i] = W->Mgrad[i] = W->search[i] = W->Ma[i] = W->Mv[i] = 0.f;
-    W->gradold[i] = W->Mgradold[i] = 0.f;
-  }
+  zero_ld_vectors<DL>(W, lane);
   SYNC();
-  // state loads as vjp_kernel's (clamped lane indices, every load before the first wait)
-  const int iq = lane < nq ? lane : max(nq - 1, 0), iv = lane < nv ? lane : max(nv - 1, 0);
-  const int iu = lane < nu ? lane : max(nu - 1, 0), ia = lane < MJL_AUX_DIM ? lane : MJL_AUX_DIM - 1;
-  const float q = nq > 0 ? S.qpos[(size_t)env * nq + iq] : 0.f;
-  const float v = nv > 0 ? S.qvel[(size_t)env * nv + iv] : 0.f;
-  const float w = nv > 0 ? S.qacc_warmstart[(size_t)env * nv + iv] : 0.f;
-  float c = nu > 0 ? V.act[(size_t)env * nu + iu] : 0.f;
-  const float t = S.time[env];
-  const float ax = S.aux[(size_t)env * MJL_AUX_DIM + ia];
-  const int perm = nu > 0 ? P.env->act_perm[iu] : 0;
-  const float sgn = nu > 0 ? P.env->act_sign[iu] : 1.f;
-  if (lane < nq) W->qpos[lane] = q;
-  if (lane < nv) { W->qvel[lane] = v; W->qacc_ws[lane] = w; }
-  if (lane == 0) W->sc[SC_TIME] = t;
-  if (lane < MJL_AUX_DIM) aux[lane] = ax;
-  // the A part's pre-step state, straight from the registers (zero past nq / nv, as the zeroed A was)
-  if (lane < MJL_MAXQ) sa[lane] = lane < nq ? q : 0.f;
-  if (lane < LD) sa[O1 + lane] = lane < nv ? v : 0.f;
-  if (lane < MJL_AUX_DIM) sa[O2 + lane] = ax;
-  {  // flip + clip the action (envs.py:335-344): act[perm[j]] from lane perm[j]
-    const bool flip = rdlane(ax, 0) > 0.5f;
-    const float ap = __shfl(c, perm);
-    c = fminf(fmaxf(flip ? ap * sgn : c, -1.f), 1.f);
-    if (lane == 0) W->sc[SC_FLIP] = ax;
+  {  // the A part's pre-step state, straight from the registers (zero past nq / nv, as the zeroed A was)
+    const LaneState s0 = load_step_state<DL, true, true>(m, S, P.env, V.act, W, aux, env, lane);
+    if (lane < MJL_MAXQ) sa[SA::qpos0 + lane] = lane < nq ? s0.q : 0.f;
+    if (lane < LD) sa[SA::qvel0 + lane] = lane < nv ? s0.v : 0.f;
+    if (lane < MJL_AUX_DIM) sa[SA::aux + lane] = s0.ax;
   }
-  if (lane < nu) W->ctrl[lane] = c;
   SYNC();
   STAMP(0, lane);
-  {
-    const KinPre kp = kin_prefetch(m, lane);
-    kinematics<DL>(m, W, lane, kp);
-    com_pos_crb<DL>(m, W, lane, kp);
-    velocity_stage<DL>(m, W, lane, kp);
-  }
-  {
-    const float x = chol_factor_solve<DL>(W->M, W->H, W->invd, nv, W->frc_smooth, lane);
-    if (lane < LD) W->qacc_smooth[lane] = (lane < nv) ? x : 0.f;
-    SYNC();
-  }
+  smooth_forward<DL, false>(m, W, lane, kin_prefetch(m, lane));
+  SYNC();
   SolveTape tp;  // (UNR)
   if constexpr (UNR) {
-    tp.t = slot + V.s_t;
-    tp.acc = (GLBA float*)(V.unr + (size_t)env * V.td.stride) + V.td.tape;
-    tp.d = V.td;
-    tp.nup = tp.nls = tp.nsets = tp.overflow = 0;
+    tp.attach<true>(slot + V.s_t, V.unr, env, V.td);  // (V.unr is non-null here: launch_vjp allocates it with vjp_unrolled)
     // the A part's 1/diag and factor: chol(M) for CG (vjp_kernel's A->Lc / invdc), zero otherwise
-    constexpr int O4 = O3 + LD, O5 = O4 + LD;
     const bool cg = m->solver != MJL_SOLVER_NEWTON;
-    for (int i = lane; i < NV * LD; i += 64) sa[O5 + i] = cg ? W->H[i] : 0.f;
-    for (int i = lane; i < LD; i += 64) sa[O4 + i] = cg ? W->invd[i] : 0.f;
+    for (int i = lane; i < NV * LD; i += 64) sa[SA::Lc + i] = cg ? W->H[i] : 0.f;
+    for (int i = lane; i < LD; i += 64) sa[SA::invdc + i] = cg ? W->invd[i] : 0.f;
   }
   GLBA f32x4* img = (GLBA f32x4*)(slot + V.s_w);
   {  // the image's union: the smooth-dynamics scratch, before the rows take its place
@@ -2393,17 +2316,8 @@ __global__ __launch_bounds__(64, 2) void vjp_record_kernel(KParams P, VjpArgs V)
       solver<DL, false>(m, W, R, lane);
     }
     sensors<DL, false>(m, W, R, lane);
-    {  // the rows into the slot's global layout (what vjp_kernel's record leaves there)
-      const Rows<true> G = global_rows<DL>(rows, P.gmax_efc, P.gmax_con);
-      const int nefc = W->nefc, ncon = W->ncon;
-      for (int i = lane; i < nefc * LD / 4; i += 64) ((GLBA f32x4*)G.J)[i] = ((const LDSA f32x4*)R.J)[i];
-      for (int i = lane; i < nefc; i += 64) {
-        G.D[i] = R.D[i]; G.aref[i] = R.aref[i]; G.jar[i] = R.jar[i]; G.force[i] = R.force[i];
-        G.Jv[i] = R.Jv[i]; G.epos[i] = R.epos[i]; G.einvw[i] = R.einvw[i]; G.emeta[i] = R.emeta[i];
-      }
-      for (int i = lane; i < ncon * CONW; i += 64) G.con[i] = R.con[i];
-      for (int i = lane; i < ncon; i += 64) { G.con_pair[i] = R.con_pair[i]; G.con_efc[i] = R.con_efc[i]; }
-    }
+    // the rows into the slot's global layout (what vjp_kernel's record leaves there)
+    copy_rows<DL>(R, global_rows<DL>(rows, P.gmax_efc, P.gmax_con), W->nefc, W->ncon, lane);
     if constexpr (!UNR) solver_hessian<DL, false>(m, W, R, lane);  // Hc at the converged active set, into H
   } else if constexpr (UNR) {
     const Rows<true> R = global_rows<DL>(rows, P.gmax_efc, P.gmax_con);
@@ -2413,7 +2327,7 @@ __global__ __launch_bounds__(64, 2) void vjp_record_kernel(KParams P, VjpArgs V)
     SYNC();
     sensors<DL, true>(m, W, R, lane);
   } else {
-    record_rows_global<DL, 2>(m, W, rows, P.gmax_efc, P.gmax_con, lane);
+    global_rows_path<DL, 2, true>(m, W, rows, P.gmax_efc, P.gmax_con, lane);
   }
   // a', 1/diag and the factor of Hc in the row area (free now), zeroed as vjp_kernel's A part is
   // (UNR: a' only; 1/diag and the factor went to the slot above)
@@ -2428,23 +2342,15 @@ __global__ __launch_bounds__(64, 2) void vjp_record_kernel(KParams P, VjpArgs V)
   integrate<DL>(m, W, lane, ab);
   STAMP(1, lane);
   SYNC();
-  for (int i = lane; i < NAB; i += 64) sa[O3 + i] = ab[i];
+  static_assert(SA::invdc == SA::ap + LD && SA::Lc == SA::ap + 2 * LD, "a', 1/diag and the factor are contiguous in the slot, as in ab");
+  for (int i = lane; i < NAB; i += 64) sa[SA::ap + i] = ab[i];
   {  // the rest of the image: the workspace up to the union
     const LDSA f32x4* src = (const LDSA f32x4*)W;
     for (int i = lane; i < U0; i += 64) img[i] = src[i];
   }
-  float* obs = P.obs + (size_t)env * P.env->obs_dim;
-  env_post<DL>(m, W, P.env, aux, obs, lane, false);
-  if (lane == 0) { P.rew[env] = W->sc[SC_REW]; P.term[env] = W->sc[SC_TERM]; P.trunc[env] = W->sc[SC_TRUNC]; }
+  env_step_outputs<DL, false>(m, W, P, aux, env, lane, false);
   SYNC();
-  if (lane < nq) S.qpos[(size_t)env * nq + lane] = W->qpos[lane];
-  if (lane < nv) {
-    S.qvel[(size_t)env * nv + lane] = W->qvel[lane];
-    S.qacc_warmstart[(size_t)env * nv + lane] = W->qacc_ws[lane];
-  }
-  if (lane < nu) S.ctrl[(size_t)env * nu + lane] = W->ctrl[lane];
-  if (lane == 0) S.time[env] = W->sc[SC_TIME];
-  if (lane < MJL_AUX_DIM) S.aux[(size_t)env * MJL_AUX_DIM + lane] = aux[lane];
+  store_step_state<DL, true>(S, W, aux, env, nq, nv, nu, lane);
   if (V.post.alive) {  // mjl_apg_post's update of this env, on the state just written back (one launch less)
     bool fin = true;
     float vmax = 0.f;

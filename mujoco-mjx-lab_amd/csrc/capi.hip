@@ -48,6 +48,25 @@ struct mjlModel {
   int nefc_max, ncon_max, nvc;  // nvc: 0 = DHum kernels, 1 = DGen kernels
 };
 
+// One env's VJP tape slot, in floats: the workspace image at w, the A part (SlotA) at a, the global row
+// slab at r, the unrolled solve's tape at t; each section starts on a multiple of 4 floats.
+struct TapeLayout { int w, a, r, t; long long stride; };
+static TapeLayout tape_layout(bool gen, int gmax_efc, int gmax_con, int iterations) {
+  // (the workspace image needs no rounding: the parenthesisation below rounds an already whole value)
+  static_assert(slot_w_floats<DGen>() % 4 == 0 && slot_w_floats<DHumV>() % 4 == 0, "WS is a whole number of b128");
+  const int LD = gen ? DGen::LD : DHumV::LD;
+  TapeDims td;
+  td.init(LD, gmax_efc, iterations);
+  const long long r4 = 3;
+  TapeLayout L;
+  L.w = 0;
+  L.a = (int)((gen ? slot_w_floats<DGen>() : slot_w_floats<DHumV>()) + r4) & ~3;
+  L.r = (int)((L.a + (gen ? slot_a_floats<DGen>() : slot_a_floats<DHumV>()) + r4) & ~3);
+  L.t = (int)(L.r + (((long long)row_slab_floats(LD, gmax_efc, gmax_con) + r4) & ~r4));
+  L.stride = ((long long)L.t + td.tape + r4) & ~r4;
+  return L;
+}
+
 struct mjlBatch {
   const mjlModel* model;
   int device, nenv, store_derived, force_global_rows;
@@ -73,8 +92,8 @@ struct mjlBatch {
   const uint32_t* reset_keys;           // per-env jax.random reset keys (mjl_env_set_reset_keys), or null
   int key_mode;
   float* d_vtape;  // MJL_OPT_VJP_TAPE: slots x nenv x vtape_stride floats (record / replay), or null
-  int vtape_slots, vt_w, vt_a, vt_r, vt_t;
-  long long vtape_stride;
+  int vtape_slots;
+  TapeLayout vt;
   float* d_rs;     // MJL_OPT_RESET_POOL: pool slots (the state fields again, [slots * nenv] rows) + obs
   int* d_pool_ctl;  // [nenv, 2] next slot, filled slots
   int pool_slots;
@@ -400,14 +419,7 @@ int mjl_batch_create(const mjlModel* model, int nenv, int device, mjlBatch** out
   size_t off = 0;
   for (int f = 0; f < MJL_NFIELD; f++) { B->field_ptr[f] = B->d_state + off; off += (size_t)dim[f] * nenv; }
   StateBuf& s = B->s;
-  s.qpos = B->field_ptr[MJL_FIELD_QPOS]; s.qvel = B->field_ptr[MJL_FIELD_QVEL];
-  s.qacc_warmstart = B->field_ptr[MJL_FIELD_QACC_WARMSTART]; s.time = B->field_ptr[MJL_FIELD_TIME];
-  s.ctrl = B->field_ptr[MJL_FIELD_CTRL]; s.aux = B->field_ptr[MJL_FIELD_AUX]; s.qacc = B->field_ptr[MJL_FIELD_QACC];
-  s.xpos = B->field_ptr[MJL_FIELD_XPOS]; s.xquat = B->field_ptr[MJL_FIELD_XQUAT];
-  s.qfrc_actuator = B->field_ptr[MJL_FIELD_QFRC_ACTUATOR]; s.sensordata = B->field_ptr[MJL_FIELD_SENSORDATA];
-  s.stats = B->field_ptr[MJL_FIELD_STATS]; s.qfrc_bias = B->field_ptr[MJL_FIELD_QFRC_BIAS];
-  s.qfrc_passive = B->field_ptr[MJL_FIELD_QFRC_PASSIVE]; s.qfrc_constraint = B->field_ptr[MJL_FIELD_QFRC_CONSTRAINT];
-  s.qacc_smooth = B->field_ptr[MJL_FIELD_QACC_SMOOTH];
+  for (int f = 0; f < MJL_NFIELD; f++) s.*kStateField[f] = B->field_ptr[f];
   // make_data: zeros, qpos = qpos0
   e = hipMemset(B->d_state, 0, total * sizeof(float));
   if (e == hipSuccess) {
@@ -424,7 +436,7 @@ int mjl_batch_create(const mjlModel* model, int nenv, int device, mjlBatch** out
   int LD = model->nvc == 0 ? DHum::LD : DGen::LD;
   B->gmax_efc = model->nefc_max > 0 ? model->nefc_max : 1;
   B->gmax_con = model->ncon_max > 0 ? model->ncon_max : 1;
-  B->scratch_stride = B->gmax_efc * (LD + 8) + B->gmax_con * (CONW + 2);
+  B->scratch_stride = row_slab_floats(LD, B->gmax_efc, B->gmax_con);
   B->scratch_stride = (B->scratch_stride + 3) & ~3;
   if (e == hipSuccess) e = hipMalloc(&B->d_scratch, (size_t)B->scratch_stride * nenv * sizeof(float));
   if (e != hipSuccess) {
@@ -469,18 +481,8 @@ int mjl_batch_set_option(mjlBatch* B, int option, int value) {
     (void)hipFree(B->d_vtape);
     B->d_vtape = nullptr; B->vtape_slots = 0;
     if (!value) return MJL_OK;
-    const bool gen = B->model->nvc != 0;
-    const int LD = gen ? DGen::LD : DHumV::LD;
-    TapeDims td;
-    td.init(LD, B->gmax_efc, B->model->desc.iterations);
-    const long long r4 = 3;
-    B->vt_w = 0;
-    B->vt_a = (int)((gen ? slot_w_floats<DGen>() : slot_w_floats<DHumV>()) + r4) & ~3;
-    B->vt_r = (int)((B->vt_a + (gen ? slot_a_floats<DGen>() : slot_a_floats<DHumV>()) + r4) & ~3);
-    const long long rows = ((long long)B->gmax_efc * (LD + 8) + (long long)B->gmax_con * (CONW + 2) + r4) & ~r4;
-    B->vt_t = (int)(B->vt_r + rows);
-    B->vtape_stride = ((long long)B->vt_t + td.tape + r4) & ~r4;
-    const size_t bytes = (size_t)value * B->nenv * (size_t)B->vtape_stride * sizeof(float);
+    B->vt = tape_layout(B->model->nvc != 0, B->gmax_efc, B->gmax_con, B->model->desc.iterations);
+    const size_t bytes = (size_t)value * B->nenv * (size_t)B->vt.stride * sizeof(float);
     hipError_t e = hipMalloc(&B->d_vtape, bytes);
     if (e != hipSuccess) { B->d_vtape = nullptr; return fail(MJL_ERR_HIP, "VJP tape (%zu bytes): %s", bytes, hipGetErrorString(e)); }
     B->vtape_slots = value;
@@ -504,16 +506,8 @@ int mjl_batch_set_option(mjlBatch* B, int option, int value) {
       B->d_rs = nullptr; B->d_pool_ctl = nullptr;
       return fail(MJL_ERR_HIP, "reset pool: %s", hipGetErrorString(e));
     }
-    float* f[MJL_NFIELD];
     size_t off = 0;
-    for (int k = 0; k < MJL_NFIELD; k++) { f[k] = B->d_rs + off; off += (size_t)B->dim[k] * rows; }
-    StateBuf& r = B->rs;
-    r.qpos = f[MJL_FIELD_QPOS]; r.qvel = f[MJL_FIELD_QVEL]; r.qacc_warmstart = f[MJL_FIELD_QACC_WARMSTART];
-    r.time = f[MJL_FIELD_TIME]; r.ctrl = f[MJL_FIELD_CTRL]; r.aux = f[MJL_FIELD_AUX]; r.qacc = f[MJL_FIELD_QACC];
-    r.xpos = f[MJL_FIELD_XPOS]; r.xquat = f[MJL_FIELD_XQUAT]; r.qfrc_actuator = f[MJL_FIELD_QFRC_ACTUATOR];
-    r.sensordata = f[MJL_FIELD_SENSORDATA]; r.stats = f[MJL_FIELD_STATS]; r.qfrc_bias = f[MJL_FIELD_QFRC_BIAS];
-    r.qfrc_passive = f[MJL_FIELD_QFRC_PASSIVE]; r.qfrc_constraint = f[MJL_FIELD_QFRC_CONSTRAINT];
-    r.qacc_smooth = f[MJL_FIELD_QACC_SMOOTH];
+    for (int k = 0; k < MJL_NFIELD; k++) { B->rs.*kStateField[k] = B->d_rs + off; off += (size_t)B->dim[k] * rows; }
     B->rs_obs = B->d_rs + total;
     B->pool_slots = value;
     return MJL_OK;
@@ -630,6 +624,11 @@ static KParams make_params(mjlBatch* B) {
   return P;
 }
 
+static void set_seed_counter(KParams& P, uint64_t seed, uint64_t counter) {
+  P.seed_lo = (uint32_t)seed; P.seed_hi = (uint32_t)(seed >> 32);
+  P.ctr_lo = (uint32_t)counter; P.ctr_hi = (uint32_t)(counter >> 32);
+}
+
 // env-step launches of at most one wave per SIMD (nenv <= 4 x CUs: C3's 1024-env rollout) take the
 // one-wave instantiation (MJL_ONE_WAVE=0 disables it, for A/B runs). Measured (profiles/r4_onewave_ab.jsonl,
 // interleaved): pooled env step at 1024 envs 81.4 -> 77.0 us, in-place 109.5 -> 106.4 us; the speed test
@@ -720,8 +719,7 @@ int mjl_env_step(mjlBatch* B, const float* act, float* obs, float* rew, float* t
   KParams P = make_params(B);
   P.in_ctrl = act; P.obs = obs; P.rew = rew; P.term = term; P.trunc = trunc;
   P.auto_reset = auto_reset;
-  P.seed_lo = (uint32_t)seed; P.seed_hi = (uint32_t)(seed >> 32);
-  P.ctr_lo = (uint32_t)counter; P.ctr_hi = (uint32_t)(counter >> 32);
+  set_seed_counter(P, seed, counter);
   if (B->d_pool_ctl && auto_reset) { P.rs = B->rs; P.rs_obs = B->rs_obs; P.pool_ctl = B->d_pool_ctl; }
   return launch<MODE_ENV_STEP>(B, P, stream);
 }
@@ -734,25 +732,15 @@ int mjl_env_fill_reset_pool(mjlBatch* B, const int* dev_n, uint64_t seed, uint64
   for (int j = 0; j < B->pool_slots; j++) {  // one launch per slot: each uses the batch's per-env scratch
     KParams P = make_params(B);
     const size_t rows = (size_t)j * B->nenv;
-    StateBuf& r = P.s;
-    r = B->rs;
-    r.qpos += rows * B->dim[MJL_FIELD_QPOS]; r.qvel += rows * B->dim[MJL_FIELD_QVEL];
-    r.qacc_warmstart += rows * B->dim[MJL_FIELD_QACC_WARMSTART]; r.time += rows * B->dim[MJL_FIELD_TIME];
-    r.ctrl += rows * B->dim[MJL_FIELD_CTRL]; r.aux += rows * B->dim[MJL_FIELD_AUX];
-    r.qacc += rows * B->dim[MJL_FIELD_QACC]; r.xpos += rows * B->dim[MJL_FIELD_XPOS];
-    r.xquat += rows * B->dim[MJL_FIELD_XQUAT]; r.qfrc_actuator += rows * B->dim[MJL_FIELD_QFRC_ACTUATOR];
-    r.sensordata += rows * B->dim[MJL_FIELD_SENSORDATA]; r.stats += rows * B->dim[MJL_FIELD_STATS];
-    r.qfrc_bias += rows * B->dim[MJL_FIELD_QFRC_BIAS]; r.qfrc_passive += rows * B->dim[MJL_FIELD_QFRC_PASSIVE];
-    r.qfrc_constraint += rows * B->dim[MJL_FIELD_QFRC_CONSTRAINT];
-    r.qacc_smooth += rows * B->dim[MJL_FIELD_QACC_SMOOTH];
+    P.s = B->rs;
+    for (int f = 0; f < MJL_NFIELD; f++) P.s.*kStateField[f] += rows * B->dim[f];
     P.obs = B->rs_obs + rows * B->obs_dim;
     P.pool_ctl = B->d_pool_ctl; P.pool_n = dev_n; P.pool_slot = j; P.pool_slots = B->pool_slots;
     P.store_derived = 1;  // the consuming step may store derived fields
     // a counter domain of its own, the slot in bits 48..55: slot j + T of one rollout and slot j of the
     // next (counter + T) stay distinct for any rollout length T
     const uint64_t c = (counter + ((uint64_t)j << 48)) ^ (1ull << 63);
-    P.seed_lo = (uint32_t)seed; P.seed_hi = (uint32_t)(seed >> 32);
-    P.ctr_lo = (uint32_t)c; P.ctr_hi = (uint32_t)(c >> 32);
+    set_seed_counter(P, seed, c);
     int rc = launch<MODE_ENV_RESET>(B, P, stream);
     if (rc != MJL_OK) return rc;
   }
@@ -794,8 +782,7 @@ int mjl_env_reset(mjlBatch* B, const float* mask, uint64_t seed, uint64_t counte
   if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
   KParams P = make_params(B);
   P.mask = mask; P.noise = noise; P.obs = obs;
-  P.seed_lo = (uint32_t)seed; P.seed_hi = (uint32_t)(seed >> 32);
-  P.ctr_lo = (uint32_t)counter; P.ctr_hi = (uint32_t)(counter >> 32);
+  set_seed_counter(P, seed, counter);
   return launch<MODE_ENV_RESET>(B, P, stream);
 }
 
@@ -807,7 +794,7 @@ template <bool ENV, int TM = 0> static int launch_vjp(mjlBatch* B, const VjpArgs
   HIPCHK(hipSetDevice(B->device));
   if (!B->d_adj_scratch) {
     const int LD = B->model->nvc == 0 ? DHum::LD : DGen::LD;
-    B->adj_row_floats = B->gmax_efc * (LD + 8) + B->gmax_con * (CONW + 2);
+    B->adj_row_floats = row_slab_floats(LD, B->gmax_efc, B->gmax_con);
     B->adj_row_floats = (B->adj_row_floats + 3) & ~3;
     B->adj_stride = B->adj_row_floats + adj_scratch_floats(B->gmax_efc, B->gmax_con);
     if (B->model->nvc == 0) B->adj_stride += DHumV::NV * DHumV::LD;  // lean unrolled replay: M-bar rows
@@ -823,45 +810,43 @@ template <bool ENV, int TM = 0> static int launch_vjp(mjlBatch* B, const VjpArgs
   KParams P = P0 ? *P0 : make_params(B);
   VjpArgs V = V0;
   V.unr = B->vjp_unrolled ? B->d_unr : nullptr;
-  V.slot_stride = B->vtape_stride;
-  V.s_w = B->vt_w; V.s_a = B->vt_a; V.s_r = B->vt_r; V.s_t = B->vt_t;
+  V.slot_stride = B->vt.stride;
+  V.s_w = B->vt.w; V.s_a = B->vt.a; V.s_r = B->vt.r; V.s_t = B->vt.t;
   V.td = B->unr_dims;
   V.scratch = B->d_adj_scratch;
   V.scratch_stride = B->adj_stride;
   V.row_floats = B->adj_row_floats;
   if (ENV && TM != 1) { V.exp = B->vjp_exp; V.exp_thr = B->vjp_exp_thr; V.exp_stage = B->d_exp_stage; }
-  dim3 grid(B->nenv), block(64);
+  // one launch of a (KParams, VjpArgs) kernel over the envs; the rest of this function is the table of
+  // which kernel runs: lean replay, LDS-row record (+- unrolled), record with its post-step update split
+  // off, default
+  const auto launch1 = [&](void (*kernel)(KParams, VjpArgs), const VjpArgs& Va) {
+    hipLaunchKernelGGL(kernel, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, P, Va);
+    return hipGetLastError();
+  };
+  const bool hum = B->model->nvc == 0;
   // the replay on the humanoid dims takes the lean layout (20 KB of LDS: one round of 8 envs per CU;
   // MJL_VJP_LEAN=0 keeps the full one, for A/B)
   static const bool lean_ok = [] { const char* e = std::getenv("MJL_VJP_LEAN"); return !(e && e[0] == '0'); }();
   if constexpr (TM == 2) {
     // (unrolled: CG only -- its reverse sweep refactors nothing; Newton's per-iteration Hessian factors
     // need the full layout's LDS)
-    if (B->model->nvc == 0 && (!B->vjp_unrolled || B->model->desc.solver == MJL_SOLVER_CG) && lean_ok) {
-      hipLaunchKernelGGL((vjp_kernel<DHumV, ENV, TM, true>), grid, block, 0, (hipStream_t)stream, P, V);
-      HIPCHK(hipGetLastError());
+    if (hum && (!B->vjp_unrolled || B->model->desc.solver == MJL_SOLVER_CG) && lean_ok) {
+      HIPCHK(launch1(vjp_kernel<DHumV, ENV, TM, true>, V));
       return MJL_OK;
     }
   }
   // the implicit record on the humanoid dims keeps its rows in LDS (vjp_record_kernel, the same slot as
   // vjp_kernel's record); MJL_OPT_FORCE_GLOBAL_ROWS keeps the global-row record (A/B, parity tests)
   if constexpr (TM == 1 && ENV) {
-    if (B->model->nvc == 0 && !B->force_global_rows) {
-      if (B->vjp_unrolled)
-        hipLaunchKernelGGL((vjp_record_kernel<DHum, DHumV, true>), grid, block, 0, (hipStream_t)stream, P, V);
-      else
-        hipLaunchKernelGGL((vjp_record_kernel<DHum, DHumV>), grid, block, 0, (hipStream_t)stream, P, V);
-      HIPCHK(hipGetLastError());
+    if (hum && !B->force_global_rows) {
+      HIPCHK(launch1(B->vjp_unrolled ? vjp_record_kernel<DHum, DHumV, true> : vjp_record_kernel<DHum, DHumV>, V));
       return MJL_OK;
     }
     if (V.post.alive) {  // the other record kernels leave the post-step update to its own launch
       VjpArgs V2 = V;
       V2.post.alive = nullptr;
-      if (B->model->nvc == 0)
-        hipLaunchKernelGGL((vjp_kernel<DHumV, ENV, TM>), grid, block, 0, (hipStream_t)stream, P, V2);
-      else
-        hipLaunchKernelGGL((vjp_kernel<DGen, ENV, TM>), grid, block, 0, (hipStream_t)stream, P, V2);
-      HIPCHK(hipGetLastError());
+      HIPCHK(launch1(hum ? vjp_kernel<DHumV, ENV, TM> : vjp_kernel<DGen, ENV, TM>, V2));
       hipLaunchKernelGGL(apg_post_kernel, dim3((B->nenv + kPostEnvs - 1) / kPostEnvs), dim3(64 * kPostEnvs), 0,
                          (hipStream_t)stream, B->s, B->model->desc.nq, B->model->desc.nv, P.rew, P.term, P.trunc,
                          V.post);
@@ -869,23 +854,57 @@ template <bool ENV, int TM = 0> static int launch_vjp(mjlBatch* B, const VjpArgs
       return MJL_OK;
     }
   }
-  if (B->model->nvc == 0)
-    hipLaunchKernelGGL((vjp_kernel<DHumV, ENV, TM>), grid, block, 0, (hipStream_t)stream, P, V);
-  else
-    hipLaunchKernelGGL((vjp_kernel<DGen, ENV, TM>), grid, block, 0, (hipStream_t)stream, P, V);
-  HIPCHK(hipGetLastError());
+  HIPCHK(launch1(hum ? vjp_kernel<DHumV, ENV, TM> : vjp_kernel<DGen, ENV, TM>, V));
   return MJL_OK;
+}
+
+// the cotangent pointers of a step VJP (null: the entry point has no such input / output)
+static VjpArgs vjp_io(const float* act, const float* g_qpos, const float* g_qvel, const float* g_ws, const float* g_rew,
+                      const float* g_aux, float* o_qpos, float* o_qvel, float* o_ws, float* o_ctrl, float* o_aux,
+                      float* nonfinite) {
+  VjpArgs V;
+  std::memset(&V, 0, sizeof(V));
+  V.act = act; V.g_qpos = g_qpos; V.g_qvel = g_qvel; V.g_rew = g_rew; V.g_aux = g_aux;
+  V.o_qpos = o_qpos; V.o_qvel = o_qvel; V.o_ctrl = o_ctrl; V.o_aux = o_aux;
+  V.g_ws = g_ws; V.o_ws = o_ws;
+  V.nonfinite = nonfinite;
+  return V;
+}
+
+// tape slot `slot` of the batch, or null with the error set
+static float* tape_slot(const mjlBatch* B, int slot) {
+  if (!B->d_vtape || slot < 0 || slot >= B->vtape_slots) {
+    fail(MJL_ERR_ARG, "VJP tape slot %d not allocated", slot);
+    return nullptr;
+  }
+  return B->d_vtape + (size_t)slot * B->nenv * (size_t)B->vt.stride;
+}
+
+// a record launch's arguments: the env step's outputs into P, the action and the (validated, tape_slot)
+// slot into the VjpArgs
+static VjpArgs record_io(mjlBatch* B, float* slot, const float* act, float* obs, float* rew, float* term, float* trunc,
+                         KParams& P) {
+  P = make_params(B);
+  P.obs = obs; P.rew = rew; P.term = term; P.trunc = trunc;
+  VjpArgs V = vjp_io(act, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  V.slot = slot;
+  return V;
+}
+
+// the env-step VJPs: the recompute (TM 0) or the replay of tape slot `slot` (TM 2)
+template <int TM> static int env_vjp(mjlBatch* B, int slot, VjpArgs V, void* stream) {
+  if (!B || !V.act || !V.g_qpos || !V.g_qvel || !V.g_rew || !V.g_aux || !V.o_qpos || !V.o_qvel || !V.o_ctrl || !V.o_aux)
+    return fail(MJL_ERR_ARG, "bad argument");
+  if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
+  if (TM == 2 && !(V.slot = tape_slot(B, slot))) return MJL_ERR_ARG;
+  return launch_vjp<true, TM>(B, V, stream);
 }
 
 extern "C" {
 
 int mjl_step_vjp(mjlBatch* B, const float* g_qpos, const float* g_qvel, float* out_qpos, float* out_qvel,
                  float* out_ctrl, void* stream) {
-  if (!B || !g_qpos || !g_qvel || !out_qpos || !out_qvel || !out_ctrl) return fail(MJL_ERR_ARG, "bad argument");
-  VjpArgs V;
-  std::memset(&V, 0, sizeof(V));
-  V.g_qpos = g_qpos; V.g_qvel = g_qvel; V.o_qpos = out_qpos; V.o_qvel = out_qvel; V.o_ctrl = out_ctrl;
-  return launch_vjp<false>(B, V, stream);
+  return mjl_step_vjp_full(B, g_qpos, g_qvel, nullptr, out_qpos, out_qvel, nullptr, out_ctrl, stream);
 }
 
 int mjl_env_step_vjp(mjlBatch* B, const float* act, const float* g_qpos, const float* g_qvel, const float* g_rew,
@@ -898,55 +917,33 @@ int mjl_env_step_vjp(mjlBatch* B, const float* act, const float* g_qpos, const f
 int mjl_env_step_vjp_guarded(mjlBatch* B, const float* act, const float* g_qpos, const float* g_qvel,
                              const float* g_rew, const float* g_aux, float* out_qpos, float* out_qvel,
                              float* out_act, float* out_aux, float* nonfinite_count, void* stream) {
-  if (!B || !act || !g_qpos || !g_qvel || !g_rew || !g_aux || !out_qpos || !out_qvel || !out_act || !out_aux)
-    return fail(MJL_ERR_ARG, "bad argument");
-  if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
-  VjpArgs V;
-  std::memset(&V, 0, sizeof(V));
-  V.act = act; V.g_qpos = g_qpos; V.g_qvel = g_qvel; V.g_rew = g_rew; V.g_aux = g_aux;
-  V.o_qpos = out_qpos; V.o_qvel = out_qvel; V.o_ctrl = out_act; V.o_aux = out_aux;
-  V.nonfinite = nonfinite_count;
-  return launch_vjp<true>(B, V, stream);
+  return mjl_env_step_vjp_full(B, act, g_qpos, g_qvel, nullptr, g_rew, g_aux, out_qpos, out_qvel, nullptr, out_act,
+                               out_aux, nonfinite_count, stream);
 }
 
 int mjl_step_vjp_full(mjlBatch* B, const float* g_qpos, const float* g_qvel, const float* g_qacc_ws,
                       float* out_qpos, float* out_qvel, float* out_qacc_ws, float* out_ctrl, void* stream) {
   if (!B || !g_qpos || !g_qvel || !out_qpos || !out_qvel || !out_ctrl) return fail(MJL_ERR_ARG, "bad argument");
-  VjpArgs V;
-  std::memset(&V, 0, sizeof(V));
-  V.g_qpos = g_qpos; V.g_qvel = g_qvel; V.o_qpos = out_qpos; V.o_qvel = out_qvel; V.o_ctrl = out_ctrl;
-  V.g_ws = g_qacc_ws; V.o_ws = out_qacc_ws;
-  return launch_vjp<false>(B, V, stream);
+  return launch_vjp<false>(B, vjp_io(nullptr, g_qpos, g_qvel, g_qacc_ws, nullptr, nullptr, out_qpos, out_qvel,
+                                     out_qacc_ws, out_ctrl, nullptr, nullptr), stream);
 }
 
 int mjl_env_step_vjp_full(mjlBatch* B, const float* act, const float* g_qpos, const float* g_qvel,
                           const float* g_qacc_ws, const float* g_rew, const float* g_aux, float* out_qpos,
                           float* out_qvel, float* out_qacc_ws, float* out_act, float* out_aux,
                           float* nonfinite_count, void* stream) {
-  if (!B || !act || !g_qpos || !g_qvel || !g_rew || !g_aux || !out_qpos || !out_qvel || !out_act || !out_aux)
-    return fail(MJL_ERR_ARG, "bad argument");
-  if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
-  VjpArgs V;
-  std::memset(&V, 0, sizeof(V));
-  V.act = act; V.g_qpos = g_qpos; V.g_qvel = g_qvel; V.g_rew = g_rew; V.g_aux = g_aux;
-  V.o_qpos = out_qpos; V.o_qvel = out_qvel; V.o_ctrl = out_act; V.o_aux = out_aux;
-  V.g_ws = g_qacc_ws; V.o_ws = out_qacc_ws;
-  V.nonfinite = nonfinite_count;
-  return launch_vjp<true>(B, V, stream);
+  return env_vjp<0>(B, -1, vjp_io(act, g_qpos, g_qvel, g_qacc_ws, g_rew, g_aux, out_qpos, out_qvel, out_qacc_ws, out_act,
+                                  out_aux, nonfinite_count), stream);
 }
 
 int mjl_env_step_record(mjlBatch* B, int slot, const float* act, float* obs, float* rew, float* term, float* trunc,
                         void* stream) {
   if (!B || !act || !obs || !rew || !term || !trunc) return fail(MJL_ERR_ARG, "bad argument");
   if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
-  if (!B->d_vtape || slot < 0 || slot >= B->vtape_slots) return fail(MJL_ERR_ARG, "VJP tape slot %d not allocated", slot);
-  KParams P = make_params(B);
-  P.obs = obs; P.rew = rew; P.term = term; P.trunc = trunc;
-  VjpArgs V;
-  std::memset(&V, 0, sizeof(V));
-  V.act = act;
-  V.slot = B->d_vtape + (size_t)slot * B->nenv * (size_t)B->vtape_stride;
-  return launch_vjp<true, 1>(B, V, stream, &P);
+  float* const sp = tape_slot(B, slot);
+  if (!sp) return MJL_ERR_ARG;
+  KParams P;
+  return launch_vjp<true, 1>(B, record_io(B, sp, act, obs, rew, term, trunc, P), stream, &P);
 }
 
 int mjl_env_step_record_apg(mjlBatch* B, int slot, const float* act, float* obs, float* rew, float* term, float* trunc,
@@ -955,13 +952,10 @@ int mjl_env_step_record_apg(mjlBatch* B, int slot, const float* act, float* obs,
   if (!B || !act || !obs || !rew || !term || !trunc || !alive || !disc || !ret || !dropped || !grew || !rfin)
     return fail(MJL_ERR_ARG, "bad argument");
   if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
-  if (!B->d_vtape || slot < 0 || slot >= B->vtape_slots) return fail(MJL_ERR_ARG, "VJP tape slot %d not allocated", slot);
-  KParams P = make_params(B);
-  P.obs = obs; P.rew = rew; P.term = term; P.trunc = trunc;
-  VjpArgs V;
-  std::memset(&V, 0, sizeof(V));
-  V.act = act;
-  V.slot = B->d_vtape + (size_t)slot * B->nenv * (size_t)B->vtape_stride;
+  float* const sp = tape_slot(B, slot);
+  if (!sp) return MJL_ERR_ARG;
+  KParams P;
+  VjpArgs V = record_io(B, sp, act, obs, rew, term, trunc, P);
   V.post = ApgPostArgs{gamma, diverge_qvel, alive, disc, ret, dropped, grew, rfin, B->nenv};
   return launch_vjp<true, 1>(B, V, stream, &P);
 }
@@ -970,18 +964,8 @@ int mjl_env_step_vjp_replay(mjlBatch* B, int slot, const float* act, const float
                             const float* g_qacc_ws, const float* g_rew, const float* g_aux, float* out_qpos,
                             float* out_qvel, float* out_qacc_ws, float* out_act, float* out_aux,
                             float* nonfinite_count, void* stream) {
-  if (!B || !act || !g_qpos || !g_qvel || !g_rew || !g_aux || !out_qpos || !out_qvel || !out_act || !out_aux)
-    return fail(MJL_ERR_ARG, "bad argument");
-  if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
-  if (!B->d_vtape || slot < 0 || slot >= B->vtape_slots) return fail(MJL_ERR_ARG, "VJP tape slot %d not allocated", slot);
-  VjpArgs V;
-  std::memset(&V, 0, sizeof(V));
-  V.act = act; V.g_qpos = g_qpos; V.g_qvel = g_qvel; V.g_rew = g_rew; V.g_aux = g_aux;
-  V.o_qpos = out_qpos; V.o_qvel = out_qvel; V.o_ctrl = out_act; V.o_aux = out_aux;
-  V.g_ws = g_qacc_ws; V.o_ws = out_qacc_ws;
-  V.nonfinite = nonfinite_count;
-  V.slot = B->d_vtape + (size_t)slot * B->nenv * (size_t)B->vtape_stride;
-  return launch_vjp<true, 2>(B, V, stream);
+  return env_vjp<2>(B, slot, vjp_io(act, g_qpos, g_qvel, g_qacc_ws, g_rew, g_aux, out_qpos, out_qvel, out_qacc_ws,
+                                    out_act, out_aux, nonfinite_count), stream);
 }
 
 }  // extern "C"
@@ -1366,18 +1350,15 @@ extern "C" int mjl_env_step_record_apg_next(mjlBatch* B, int slot, const float* 
       !on || !alive_snap || (use_norm && (!mean || !var)))
     return fail(MJL_ERR_ARG, "bad argument");
   if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
-  if (!B->d_vtape || slot < 0 || slot >= B->vtape_slots) return fail(MJL_ERR_ARG, "VJP tape slot %d not allocated", slot);
+  float* const sp = tape_slot(B, slot);
+  if (!sp) return MJL_ERR_ARG;
   if (!mjl_env_record_fused(B)) return fail(MJL_ERR_UNSUPPORTED, "record_apg_next: the humanoid dims' record only");
   const int nq = B->model->desc.nq, nv = B->model->desc.nv;
   SmallMlp P;
   int rc = small_mlp_setup(B->nenv, nq + nv, nl, widths, w_t, b, ys, P, true);
   if (rc != MJL_OK) return rc;
-  KParams Pk = make_params(B);
-  Pk.obs = obs; Pk.rew = rew; Pk.term = term; Pk.trunc = trunc;
-  VjpArgs V;
-  std::memset(&V, 0, sizeof(V));
-  V.act = act;
-  V.slot = B->d_vtape + (size_t)slot * B->nenv * (size_t)B->vtape_stride;
+  KParams Pk;
+  VjpArgs V = record_io(B, sp, act, obs, rew, term, trunc, Pk);
   V.post = ApgPostArgs{gamma, diverge_qvel, alive, disc, ret, dropped, grew, rfin, B->nenv};
   V.next = ApgNextArgs{use_norm, mean, var, o, on, alive_snap, P};
   return launch_vjp<true, 1>(B, V, stream, &Pk);
@@ -1396,7 +1377,8 @@ extern "C" int mjl_env_step_vjp_replay_apg(mjlBatch* B, int slot, const float* a
       !alive_snap || !w || !w[0] || (use_norm && (!mean || !var)))
     return fail(MJL_ERR_ARG, "bad argument");
   if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
-  if (!B->d_vtape || slot < 0 || slot >= B->vtape_slots) return fail(MJL_ERR_ARG, "VJP tape slot %d not allocated", slot);
+  float* const sp = tape_slot(B, slot);
+  if (!sp) return MJL_ERR_ARG;
   const int nq = B->model->desc.nq, nv = B->model->desc.nv;
   SmallMlp Pm;
   const float* nob[kSmlMaxL] = {w[0], w[0], w[0], w[0]};  // biases unused by the backward
@@ -1404,13 +1386,9 @@ extern "C" int mjl_env_step_vjp_replay_apg(mjlBatch* B, int slot, const float* a
   if (rc != MJL_OK) return rc;
   if (Pm.n[nl - 1] > 32 || B->model->desc.nu != Pm.n[nl - 1])
     return fail(MJL_ERR_ARG, "replay_apg: the policy's output width must be the action width (<= 32)");
-  VjpArgs V;
-  std::memset(&V, 0, sizeof(V));
-  V.act = act; V.g_qpos = g_qpos; V.g_qvel = g_qvel; V.g_rew = g_rew; V.g_aux = g_aux;
-  V.o_qpos = out_qpos; V.o_qvel = out_qvel; V.o_ctrl = out_act; V.o_aux = out_aux;
-  V.g_ws = g_qacc_ws; V.o_ws = out_qacc_ws;
-  V.nonfinite = nonfinite_count;
-  V.slot = B->d_vtape + (size_t)slot * B->nenv * (size_t)B->vtape_stride;
+  VjpArgs V = vjp_io(act, g_qpos, g_qvel, g_qacc_ws, g_rew, g_aux, out_qpos, out_qvel, out_qacc_ws, out_act, out_aux,
+                     nonfinite_count);
+  V.slot = sp;
   V.pbwd = ApgPolicyBwd{use_norm, o, mean, var, alive_snap, Pm};
   return launch_vjp<true, 2>(B, V, stream);
 }

@@ -130,6 +130,20 @@ struct StateBuf {
   float *qacc, *xpos, *xquat, *qfrc_actuator, *sensordata, *stats;
   float *qfrc_bias, *qfrc_passive, *qfrc_constraint, *qacc_smooth;
 };
+// the member behind each MJL_FIELD_* index, in index order (host side: the kernels name the members)
+inline constexpr float* StateBuf::*kStateField[] = {
+    &StateBuf::qpos,           &StateBuf::qvel,         &StateBuf::qacc_warmstart,  &StateBuf::time,
+    &StateBuf::ctrl,           &StateBuf::qacc,         &StateBuf::xpos,            &StateBuf::xquat,
+    &StateBuf::qfrc_actuator,  &StateBuf::sensordata,   &StateBuf::aux,             &StateBuf::stats,
+    &StateBuf::qfrc_bias,      &StateBuf::qfrc_passive, &StateBuf::qfrc_constraint, &StateBuf::qacc_smooth};
+static_assert(sizeof(kStateField) / sizeof(kStateField[0]) == MJL_NFIELD && sizeof(StateBuf) == MJL_NFIELD * sizeof(float*),
+              "one StateBuf member per field");
+static_assert(MJL_FIELD_QPOS == 0 && MJL_FIELD_QVEL == 1 && MJL_FIELD_QACC_WARMSTART == 2 && MJL_FIELD_TIME == 3 &&
+                  MJL_FIELD_CTRL == 4 && MJL_FIELD_QACC == 5 && MJL_FIELD_XPOS == 6 && MJL_FIELD_XQUAT == 7 &&
+                  MJL_FIELD_QFRC_ACTUATOR == 8 && MJL_FIELD_SENSORDATA == 9 && MJL_FIELD_AUX == 10 &&
+                  MJL_FIELD_STATS == 11 && MJL_FIELD_QFRC_BIAS == 12 && MJL_FIELD_QFRC_PASSIVE == 13 &&
+                  MJL_FIELD_QFRC_CONSTRAINT == 14 && MJL_FIELD_QACC_SMOOTH == 15,
+              "kStateField is in MJL_FIELD_* order");
 
 struct KParams {
   const ModelF* m;

@@ -268,32 +268,52 @@ template <bool G> struct Rows {
   I *emeta, *con_pair, *con_efc;
   int cap, capc;
 };
+// The row arrays behind J (one float / int per constraint row) and behind con (one per contact), in
+// slab order: lds_rows, global_rows, row_slab_floats and copy_rows are all written over these two
+// lists, so an array added to Rows<G> is added here and reaches all four.
+#define MJL_EFC_ARRAYS(X) X(F, D) X(F, aref) X(F, jar) X(F, force) X(F, Jv) X(F, epos) X(F, einvw) X(I, emeta)
+#define MJL_CON_ARRAYS(X) X(I, con_pair) X(I, con_efc)
+#define MJL_COUNT_(T, f) +1
+constexpr int kEfcArrays = 0 MJL_EFC_ARRAYS(MJL_COUNT_), kConArrays = 0 MJL_CON_ARRAYS(MJL_COUNT_);
+static_assert(sizeof(Rows<true>) == (2 + kEfcArrays + kConArrays) * sizeof(void*) + 2 * sizeof(int),
+              "Rows<G> holds J, con and the listed arrays");
 template <class D> INL Rows<false> lds_rows(LDSA WS<D>* W) {
   Rows<false> R;
-  R.J = W->J; R.D = W->D; R.aref = W->aref; R.jar = W->jar; R.force = W->force; R.Jv = W->Jv;
-  R.epos = W->epos; R.einvw = W->einvw; R.emeta = W->emeta; R.con = W->con; R.con_pair = W->con_pair;
-  R.con_efc = W->con_efc; R.cap = D::CAP; R.capc = D::CAPC;
+  R.J = W->J; R.con = W->con;
+#define X(T, f) R.f = W->f;
+  MJL_EFC_ARRAYS(X) MJL_CON_ARRAYS(X)
+#undef X
+  R.cap = D::CAP; R.capc = D::CAPC;
   return R;
 }
+// floats of one env's global row slab: J [nefc_max][LD], the per-row arrays, con [ncon_max][CONW], the
+// per-contact arrays (the walk of global_rows): nefc_max * (LD + 8) + ncon_max * (CONW + 2) with today's lists
+__host__ __device__ constexpr int row_slab_floats(int LD, int nefc_max, int ncon_max) {
+  return nefc_max * (LD + kEfcArrays) + ncon_max * (CONW + kConArrays);
+}
 template <class D> INL Rows<true> global_rows(float* base_generic, int nefc_max, int ncon_max) {
-  constexpr int LD = D::LD;
   GLBA float* p = (GLBA float*)base_generic;
   Rows<true> R;
-  R.J = p; p += nefc_max * LD;
-  R.D = p; p += nefc_max;
-  R.aref = p; p += nefc_max;
-  R.jar = p; p += nefc_max;
-  R.force = p; p += nefc_max;
-  R.Jv = p; p += nefc_max;
-  R.epos = p; p += nefc_max;
-  R.einvw = p; p += nefc_max;
-  R.emeta = (GLBA int*)p; p += nefc_max;
+  R.J = p; p += nefc_max * D::LD;
+#define X(T, f) R.f = (Rows<true>::T*)p; p += nefc_max;
+  MJL_EFC_ARRAYS(X)
+#undef X
   R.con = p; p += ncon_max * CONW;
-  R.con_pair = (GLBA int*)p; p += ncon_max;
-  R.con_efc = (GLBA int*)p;
+#define X(T, f) R.f = (Rows<true>::T*)p; p += ncon_max;
+  MJL_CON_ARRAYS(X)
+#undef X
   R.cap = nefc_max; R.capc = ncon_max;
   return R;
 }
+// the first nefc rows / ncon contacts of the LDS rows into a global slab
+#define X(T, f) G.f[i] = S.f[i];
+template <class D> INL void copy_rows(const Rows<false>& S, const Rows<true>& G, int nefc, int ncon, int lane) {
+  for (int i = lane; i < nefc * D::LD / 4; i += 64) ((GLBA f32x4*)G.J)[i] = ((const LDSA f32x4*)S.J)[i];
+  for (int i = lane; i < nefc; i += 64) { MJL_EFC_ARRAYS(X) }
+  for (int i = lane; i < ncon * CONW; i += 64) G.con[i] = S.con[i];
+  for (int i = lane; i < ncon; i += 64) { MJL_CON_ARRAYS(X) }
+}
+#undef X
 
 // ---------------------------------------------------------------------------------------------
 // small math (MuJoCo conventions: quat [w x y z], spatial vectors [ang; lin], row-major 3x3)
@@ -2111,30 +2131,39 @@ template <class D, bool G> PHASE void sensors(MP m_, LDSA WS<D>* W, Rows<G> R, i
 // rows that do not fit in LDS: the cold path, kept out of line
 // MW: the calling kernel's waves-per-SIMD bound. A callee shared by kernels of different bounds is
 // compiled for the loosest, and its register use then caps the tighter kernel's occupancy.
-template <class D, int MW = MJL_MINWAVES> NOINL void global_rows_path(MP m, LDSA WS<D>* W, float* scratch_env, int gmax_efc, int gmax_con,
-                                               int lane) {
+// HESS (the implicit VJP's record): then the Hessian at the converged active set, into H. A template
+// flag, so each (MW, HESS) caller keeps an instantiation of its own.
+template <class D, int MW = MJL_MINWAVES, bool HESS = false>
+NOINL void global_rows_path(MP m, LDSA WS<D>* W, float* scratch_env, int gmax_efc, int gmax_con, int lane) {
   Rows<true> R = global_rows<D>(scratch_env, gmax_efc, gmax_con);
   build_rows<D, true>(m, W, R, lane);
   solver<D, true>(m, W, R, lane);
   sensors<D, true>(m, W, R, lane);
+  if constexpr (HESS) solver_hessian<D, true>(m, W, R, lane);
+}
+
+// the smooth dynamics: kinematics through qacc_smooth (no barrier after the last store: the caller's, or
+// build_rows', comes before its first read). STAMPS: forward()'s phase stamps of the timing build.
+template <class D, bool STAMPS> INL void smooth_forward(MP m, LDSA WS<D>* W, int lane, const KinPre& kp) {
+  constexpr int LD = D::LD;
+  if constexpr (STAMPS) STAMP(0, lane);
+  kinematics<D>(m, W, lane, kp);
+  if constexpr (STAMPS) STAMP(1, lane);
+  com_pos_crb<D>(m, W, lane, kp);
+  if constexpr (STAMPS) STAMP(2, lane);
+  velocity_stage<D>(m, W, lane, kp);
+  if constexpr (STAMPS) STAMP(3, lane);
+  // factor M into H: qacc_smooth now, CG preconditioner later
+  float x = chol_factor_solve<D>(W->M, W->H, W->invd, m->nv, W->frc_smooth, lane);
+  if (lane < LD) W->qacc_smooth[lane] = (lane < m->nv) ? x : 0.f;
+  if constexpr (STAMPS) STAMP(4, lane);
 }
 
 // full forward pass (mjx.forward)
 template <class D, int MW = MJL_MINWAVES> PHASE void forward(MP m_, LDSA WS<D>* W, float* scratch_env, int gmax_efc, int gmax_con,
                                       int force_global, int lane, const KinPre& kp) {
   MP m = uniform_ptr(m_);
-  constexpr int LD = D::LD;
-  STAMP(0, lane);
-  kinematics<D>(m, W, lane, kp);
-  STAMP(1, lane);
-  com_pos_crb<D>(m, W, lane, kp);
-  STAMP(2, lane);
-  velocity_stage<D>(m, W, lane, kp);
-  STAMP(3, lane);
-  // factor M into H: qacc_smooth now, CG preconditioner later
-  float x = chol_factor_solve<D>(W->M, W->H, W->invd, m->nv, W->frc_smooth, lane);
-  if (lane < LD) W->qacc_smooth[lane] = (lane < m->nv) ? x : 0.f;  // first read after build_rows' barriers
-  STAMP(4, lane);
+  smooth_forward<D, true>(m, W, lane, kp);
   bool ok = false;
   if (!force_global) ok = build_rows<D, false>(m, W, lds_rows<D>(W), lane);
   STAMP(5, lane);
@@ -2520,6 +2549,85 @@ template <class D> INL void rs_load(MP m, const CSTA KParams* Pk, LDSA WS<D>* W,
 }
 
 // ---------------------------------------------------------------------------------------------
+// the step's prologue and epilogue, shared by step_kernel and the VJP's record kernels (adjoint.hip),
+// whose steps are bit for bit the env step (tests/test_vjp_tape.py)
+// ---------------------------------------------------------------------------------------------
+// vectors beyond nv must read as zero in the LD-wide row kernels
+template <class D, class WT> INL void zero_ld_vectors(LDSA WT* W, int lane) {
+  for (int i = lane; i < D::LD; i += 64) {
+    W->qvel[i] = 0.f; W->qacc_ws[i] = 0.f;
+    W->frc_bias[i] = W->frc_passive[i] = W->frc_act[i] = W->frc_smooth[i] = W->qacc_smooth[i] = 0.f;
+    W->qacc[i] = W->frc_con[i] = W->grad[i] = W->Mgrad[i] = W->search[i] = W->Ma[i] = W->Mv[i] = 0.f;
+    W->gradold[i] = W->Mgradold[i] = 0.f;
+  }
+}
+
+// The pre-step state of env `env` into the workspace (control from csrc, [nenv, nu]); ENV: the aux row
+// into `aux` and the action flipped + clipped (envs.py:335-344), FLIP_SC: aux[0] into sc[SC_FLIP].
+// Every load issues before the first wait: clamped lane indices instead of a branch around each load
+// (each branch waited for its own load: ~7 dependent HBM round trips per env step); a zero-size field
+// clamps to index 0 and is not read (no load before a user buffer's start). Returns this lane's loaded
+// qpos / qvel / aux entries (clamped lanes: a copy of the last one), for the VJP's A part.
+struct LaneState { float q, v, ax; };
+template <class D, bool ENV, bool FLIP_SC> INL LaneState load_step_state(MP m, const StateBuf& S, const mjlEnvConfig* cfg,
+                                                                         const float* csrc, LDSA WS<D>* W, LDSA float* aux,
+                                                                         int env, int lane) {
+  const int nq = m->nq, nv = m->nv, nu = m->nu;
+  const int iq = lane < nq ? lane : max(nq - 1, 0), iv = lane < nv ? lane : max(nv - 1, 0);
+  const int iu = lane < nu ? lane : max(nu - 1, 0);
+  const float q = nq > 0 ? S.qpos[(size_t)env * nq + iq] : 0.f;
+  const float v = nv > 0 ? S.qvel[(size_t)env * nv + iv] : 0.f;
+  const float w = nv > 0 ? S.qacc_warmstart[(size_t)env * nv + iv] : 0.f;
+  float c = nu > 0 ? csrc[(size_t)env * nu + iu] : 0.f;
+  const float t = S.time[env];
+  float ax = 0.f, sgn = 1.f;
+  int perm = iu;
+  if (ENV) {
+    const int ia = lane < MJL_AUX_DIM ? lane : MJL_AUX_DIM - 1;
+    ax = S.aux[(size_t)env * MJL_AUX_DIM + ia];
+    perm = nu > 0 ? cfg->act_perm[iu] : 0;
+    sgn = nu > 0 ? cfg->act_sign[iu] : 1.f;
+  }
+  if (lane < nq) W->qpos[lane] = q;
+  if (lane < nv) { W->qvel[lane] = v; W->qacc_ws[lane] = w; }
+  if (lane == 0) W->sc[SC_TIME] = t;
+  if (ENV) {  // act[perm[j]] from lane perm[j]
+    if (lane < MJL_AUX_DIM) aux[lane] = ax;
+    const bool flip = rdlane(ax, 0) > 0.5f;
+    const float ap = __shfl(c, perm);
+    c = fminf(fmaxf(flip ? ap * sgn : c, -1.f), 1.f);
+    if (FLIP_SC && lane == 0) W->sc[SC_FLIP] = ax;
+  }
+  if (lane < nu) W->ctrl[lane] = c;
+  return LaneState{q, v, ax};
+}
+
+// the env step's outputs, auto-reset aside: env_post, then reward / termination / truncation; returns
+// the env's observation row. P: the launch's KParams in whatever address space the caller reads them
+// from (by reference: see env_reset on what by-value copies cost). STAMPS: step_kernel's stamp 37.
+template <class D, bool STAMPS, class KP> INL float* env_step_outputs(MP m, LDSA WS<D>* W, KP& P, LDSA float* aux, int env,
+                                                                      int lane, bool skip_done_obs) {
+  float* obs = P.obs + (size_t)env * P.env->obs_dim;
+  env_post<D>(m, W, P.env, aux, obs, lane, skip_done_obs);
+  if constexpr (STAMPS) STAMP(37, lane);
+  if (lane == 0) { P.rew[env] = W->sc[SC_REW]; P.term[env] = W->sc[SC_TERM]; P.trunc[env] = W->sc[SC_TRUNC]; }
+  return obs;
+}
+
+// the post-step state back to the batch (AUX: with the env's aux row)
+template <class D, bool AUX, class SB> INL void store_step_state(SB& S, LDSA WS<D>* W, LDSA float* aux, int env, int nq,
+                                                                 int nv, int nu, int lane) {
+  if (lane < nq) S.qpos[(size_t)env * nq + lane] = W->qpos[lane];
+  if (lane < nv) {
+    S.qvel[(size_t)env * nv + lane] = W->qvel[lane];
+    S.qacc_warmstart[(size_t)env * nv + lane] = W->qacc_ws[lane];
+  }
+  if (lane < nu) S.ctrl[(size_t)env * nu + lane] = W->ctrl[lane];
+  if (lane == 0) S.time[env] = W->sc[SC_TIME];
+  if (AUX && lane < MJL_AUX_DIM) S.aux[(size_t)env * MJL_AUX_DIM + lane] = aux[lane];
+}
+
+// ---------------------------------------------------------------------------------------------
 // the kernel: one workgroup (= one wavefront) per env
 // ---------------------------------------------------------------------------------------------
 // MW = the waves-per-SIMD bound of the launch: 2 (the full-occupancy launches: 2048 envs resident on
@@ -2532,7 +2640,6 @@ template <class D, int MODE, int MW = MJL_MINWAVES> __global__ __launch_bounds__
   __shared__ float aux_s[MJL_AUX_DIM + 3];
   LDSA WS<D>* W = (LDSA WS<D>*)&Ws;
   LDSA float* aux = (LDSA float*)aux_s;
-  constexpr int LD = D::LD;
   MP m = (MP)P.m;
   const int env = block_env();
   const int lane = threadIdx.x;
@@ -2547,13 +2654,7 @@ template <class D, int MODE, int MW = MJL_MINWAVES> __global__ __launch_bounds__
   const int nq = m->nq, nv = m->nv, nu = m->nu;
   const StateBuf& S = P.s;
   float* const scratch_env = P.scratch + (size_t)env * (size_t)P.scratch_stride;
-  // vectors beyond nv must read as zero in the LD-wide row kernels
-  for (int i = lane; i < LD; i += 64) {
-    W->qvel[i] = 0.f; W->qacc_ws[i] = 0.f;
-    W->frc_bias[i] = W->frc_passive[i] = W->frc_act[i] = W->frc_smooth[i] = W->qacc_smooth[i] = 0.f;
-    W->qacc[i] = W->frc_con[i] = W->grad[i] = W->Mgrad[i] = W->search[i] = W->Ma[i] = W->Mv[i] = 0.f;
-    W->gradold[i] = W->Mgradold[i] = 0.f;
-  }
+  zero_ld_vectors<D>(W, lane);
   SYNC();
 
   if (MODE == MODE_ENV_RESET) {
@@ -2566,36 +2667,8 @@ template <class D, int MODE, int MW = MJL_MINWAVES> __global__ __launch_bounds__
       if (lane < nu) W->ctrl[lane] = 0.f;
       if (lane == 0) W->sc[SC_TIME] = 0.f;
     } else {
-      // every state load issues before the first wait: clamped lane indices instead of a branch around
-      // each load (each branch waited for its own load: ~7 dependent HBM round trips per env step)
-      // (a zero-size field clamps to index 0 and is not read: no load before a user buffer's start)
-      const int iq = lane < nq ? lane : max(nq - 1, 0), iv = lane < nv ? lane : max(nv - 1, 0);
-      const int iu = lane < nu ? lane : max(nu - 1, 0);
-      const float q = nq > 0 ? S.qpos[(size_t)env * nq + iq] : 0.f;
-      const float v = nv > 0 ? S.qvel[(size_t)env * nv + iv] : 0.f;
-      const float w = nv > 0 ? S.qacc_warmstart[(size_t)env * nv + iv] : 0.f;
       const float* csrc = (MODE == MODE_ENV_STEP || (MODE == MODE_STEP && P.in_ctrl)) ? P.in_ctrl : S.ctrl;
-      float c = nu > 0 ? csrc[(size_t)env * nu + iu] : 0.f;
-      const float t = S.time[env];
-      float ax = 0.f, sgn = 1.f;
-      int perm = iu;
-      if (MODE == MODE_ENV_STEP) {
-        const int ia = lane < MJL_AUX_DIM ? lane : MJL_AUX_DIM - 1;
-        ax = S.aux[(size_t)env * MJL_AUX_DIM + ia];
-        perm = nu > 0 ? P.env->act_perm[iu] : 0;
-        sgn = nu > 0 ? P.env->act_sign[iu] : 1.f;
-      }
-      if (lane < nq) W->qpos[lane] = q;
-      if (lane < nv) { W->qvel[lane] = v; W->qacc_ws[lane] = w; }
-      if (lane == 0) W->sc[SC_TIME] = t;
-      if (MODE == MODE_ENV_STEP) {  // flip + clip the action (envs.py:335-344): act[perm[j]] from lane perm[j]
-        if (lane < MJL_AUX_DIM) aux[lane] = ax;
-        const bool flip = rdlane(ax, 0) > 0.5f;
-        const float ap = __shfl(c, perm);
-        c = fminf(fmaxf(flip ? ap * sgn : c, -1.f), 1.f);
-        if (lane == 0) W->sc[SC_FLIP] = ax;
-      }
-      if (lane < nu) W->ctrl[lane] = c;
+      load_step_state<D, MODE == MODE_ENV_STEP, true>(m, S, P.env, csrc, W, aux, env, lane);
     }
     SYNC();
     forward<D, MW>(m, W, scratch_env, P.gmax_efc, P.gmax_con, P.force_global_rows, lane, kp);
@@ -2603,10 +2676,7 @@ template <class D, int MODE, int MW = MJL_MINWAVES> __global__ __launch_bounds__
     STAMP(8, lane);
     const CSTA KParams& P = *kparams_late();  // the tail's arguments, loaded here (see kparams_late)
     if (MODE == MODE_ENV_STEP) {
-      float* obs = P.obs + (size_t)env * P.env->obs_dim;
-      env_post<D>(m, W, P.env, aux, obs, lane, P.auto_reset != 0);
-      STAMP(37, lane);
-      if (lane == 0) { P.rew[env] = W->sc[SC_REW]; P.term[env] = W->sc[SC_TERM]; P.trunc[env] = W->sc[SC_TRUNC]; }
+      float* obs = env_step_outputs<D, true>(m, W, P, aux, env, lane, P.auto_reset != 0);
       bool bad = (lane < nq && !isfinite(W->qpos[lane])) || (lane < nv && !isfinite(W->qvel[lane]));
       bool anybad = __ballot(bad) != 0ull;
       if (lane == 0) W->sc[SC_NAN] = anybad ? 1.f : 0.f;
@@ -2636,17 +2706,8 @@ template <class D, int MODE, int MW = MJL_MINWAVES> __global__ __launch_bounds__
     return;
   }
   if (MODE == MODE_FORWARD && lane < nv) S.qacc_warmstart[(size_t)env * nv + lane] = W->qacc_ws[lane];
-  if (MODE != MODE_FORWARD) {
-    if (lane < nq) S.qpos[(size_t)env * nq + lane] = W->qpos[lane];
-    if (lane < nv) {
-      S.qvel[(size_t)env * nv + lane] = W->qvel[lane];
-      S.qacc_warmstart[(size_t)env * nv + lane] = W->qacc_ws[lane];
-    }
-    if (lane < nu) S.ctrl[(size_t)env * nu + lane] = W->ctrl[lane];
-    if (lane == 0) S.time[env] = W->sc[SC_TIME];
-    if ((MODE == MODE_ENV_STEP || MODE == MODE_ENV_RESET) && lane < MJL_AUX_DIM)
-      S.aux[(size_t)env * MJL_AUX_DIM + lane] = aux[lane];
-  }
+  if (MODE != MODE_FORWARD)
+    store_step_state<D, MODE == MODE_ENV_STEP || MODE == MODE_ENV_RESET>(S, W, aux, env, nq, nv, nu, lane);
   if (MODE == MODE_FORWARD || P.store_derived) {
     if (lane < nv) {
       size_t o = (size_t)env * nv + lane;
