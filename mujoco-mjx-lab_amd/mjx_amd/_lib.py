@@ -11,33 +11,27 @@ import os
 import subprocess
 
 from . import _srchash, abi
+from ._header import HEADER, SCALARS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MJX355_LIB", os.path.join(_HERE, "libmjx355.so"))  # override: A/B builds
 CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 
-# every symbol include/mjx355.h declares
-EXPORTS = [
-    "mjl_last_error", "mjl_version", "mjl_model_create", "mjl_model_destroy", "mjl_model_nefc_max",
-    "mjl_batch_create", "mjl_batch_destroy", "mjl_batch_nenv", "mjl_batch_set_option", "mjl_get", "mjl_set",
-    "mjl_forward", "mjl_step", "mjl_speedtest_step", "mjl_env_config", "mjl_env_step", "mjl_env_reset",
-    "mjl_step_vjp", "mjl_env_step_vjp", "mjl_gae", "mjl_batch_set_counter_base",
-    "mjl_env_set_reset_keys", "mjl_prng_split", "mjl_env_step_vjp_guarded", "mjl_state_size", "mjl_get_state",
-    "mjl_set_state", "mjl_obs_normalize", "mjl_policy_head", "mjl_colsum_scratch", "mjl_colsum", "mjl_tanh_bwd_colsum", "mjl_slice_sum", "mjl_tanh_inplace", "mjl_small_mlp_fwd",
-    "mjl_small_mlp_bwd_input", "mjl_apg_obs_policy_fwd", "mjl_apg_policy_bwd_obs_vjp",
-    "mjl_policy_param_floats", "mjl_policy_fwd",
-    "mjl_step_vjp_full", "mjl_env_step_vjp_full", "mjl_env_fill_reset_pool",
-    "mjl_apg_obs", "mjl_apg_post", "mjl_apg_obs_vjp", "mjl_env_step_record", "mjl_env_step_record_apg",
-    "mjl_env_step_record_apg_next", "mjl_env_record_fused", "mjl_env_step_vjp_replay", "mjl_env_step_vjp_replay_apg",
-    "mjl_ppo_loss_scratch", "mjl_ppo_surrogate", "mjl_mse", "mjl_gather_rows", "mjl_adam",
-    "mjl_adam_dev", "mjl_vjp_scale_attach",
-    "mjl_colsum_batched_scratch", "mjl_colsum_batched", "mjl_tanh_bwd_colsum_batched", "mjl_slice_sum_batched",
-    "mjl_mse_strided", "mjl_ppo_surrogate_clipped", "mjl_bias_act", "mjl_adam_multi",
-    "mjl_gather_rows_indexed", "mjl_slice_sum_multi", "mjl_tanh_bwd_colsum_partials", "mjl_twin_loss_head_blocks", "mjl_twin_loss_head",
-    "mjl_twin_fused_shapes", "mjl_twin_gather_in", "mjl_twin_head_bwd", "mjl_twin_head_blocks", "mjl_twin_head",
-]
+# every symbol include/mjx355.h declares, in header order
+EXPORTS = [name for _, name, _ in HEADER.protos]
+
+# C type of the header -> ctypes: the two structs and the handle outputs are typed, every other pointer
+# (buffers, pointer tables, `void* stream`) is an address, scalars are SCALARS
+_TYPED = {"mjlModelDesc*": C.POINTER(abi.ModelDesc), "mjlEnvConfig*": C.POINTER(abi.EnvConfigC),
+          "mjlModel**": C.POINTER(C.c_void_p), "mjlBatch**": C.POINTER(C.c_void_p)}
+_RETURNS = {"void": None, "char*": C.c_char_p}
+_ERRORS = {v: k for k, v in HEADER.enums.items() if k.startswith("MJL_ERR_")}
 
 _lib = None
+
+
+def _ctype(t: str):
+    return _TYPED.get(t) or (C.c_void_p if t.endswith("*") else SCALARS[t])
 
 
 class MjlError(RuntimeError):
@@ -86,101 +80,14 @@ def lib() -> C.CDLL:
         if built != tree:
             raise MjlError(f"stale native library {LIB_PATH}: built from sources {built or '(unstamped)'}, "
                            f"the tree's sources are {tree} (rebuild: make -C {CSRC})")
-    P, vp, f32p, i32 = C.POINTER, C.c_void_p, C.c_void_p, C.c_int
-    u64 = C.c_uint64
-    L.mjl_last_error.restype = C.c_char_p
-    L.mjl_version.restype = C.c_char_p
-    L.mjl_model_create.argtypes = [P(abi.ModelDesc), P(vp)]
-    L.mjl_model_destroy.argtypes = [vp]
-    L.mjl_model_destroy.restype = None
-    L.mjl_model_nefc_max.argtypes = [vp]
-    L.mjl_batch_create.argtypes = [vp, i32, i32, P(vp)]
-    L.mjl_batch_destroy.argtypes = [vp]
-    L.mjl_batch_destroy.restype = None
-    L.mjl_batch_nenv.argtypes = [vp]
-    L.mjl_batch_set_option.argtypes = [vp, i32, i32]
-    L.mjl_get.argtypes = [vp, i32, f32p, vp]
-    L.mjl_set.argtypes = [vp, i32, f32p, f32p, vp]
-    L.mjl_forward.argtypes = [vp, f32p, vp]
-    L.mjl_step.argtypes = [vp, f32p, vp]
-    L.mjl_speedtest_step.argtypes = [vp, f32p, f32p, vp]
-    L.mjl_env_config.argtypes = [vp, P(abi.EnvConfigC)]
-    L.mjl_env_step.argtypes = [vp, f32p, f32p, f32p, f32p, f32p, i32, u64, u64, vp]
-    L.mjl_env_reset.argtypes = [vp, f32p, u64, u64, f32p, f32p, vp]
-    L.mjl_env_fill_reset_pool.argtypes = [vp, vp, u64, u64, vp]
-    L.mjl_ppo_loss_scratch.restype = C.c_longlong
-    L.mjl_ppo_loss_scratch.argtypes = [i32, i32]
-    L.mjl_ppo_surrogate.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp]
-    L.mjl_mse.argtypes = [vp, vp, i32, vp, vp, vp, vp]
-    L.mjl_gather_rows.argtypes = [vp, i32, C.c_longlong, i32, vp, vp, vp, vp]
-    L.mjl_adam.argtypes = [i32, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, i32, vp]
-    L.mjl_adam_dev.argtypes = [i32, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp]
-    L.mjl_env_step_record.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
-    L.mjl_env_step_record_apg.argtypes = [vp, i32, vp, vp, vp, vp, vp, C.c_float, C.c_float] + [vp] * 7
-    L.mjl_env_record_fused.argtypes = [vp]
-    L.mjl_env_step_vjp_replay_apg.argtypes = [vp, i32] + [vp] * 12 + [i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
-    L.mjl_env_step_record_apg_next.argtypes = ([vp, i32, vp, vp, vp, vp, vp, C.c_float, C.c_float] + [vp] * 8 +
-                                               [i32, vp, vp, vp, i32, vp, vp, vp, vp, vp])
-    L.mjl_env_step_vjp_replay.argtypes = [vp, i32] + [vp] * 12 + [vp]
-    L.mjl_apg_obs.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp]
-    L.mjl_apg_post.argtypes = [vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp]
-    L.mjl_apg_obs_vjp.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
-    L.mjl_batch_set_counter_base.argtypes = [vp, vp]
-    L.mjl_env_set_reset_keys.argtypes = [vp, vp, i32]
-    L.mjl_vjp_scale_attach.argtypes = [vp, vp, i32]
-    L.mjl_env_step_vjp_guarded.argtypes = [vp] + [vp] * 10 + [vp]
-    L.mjl_state_size.argtypes = [vp]
-    L.mjl_get_state.argtypes = [vp, vp, vp]
-    L.mjl_set_state.argtypes = [vp, vp, vp, vp]
-    L.mjl_prng_split.argtypes = [vp, i32, i32, i32, vp, vp]
-    L.mjl_gae.argtypes = [f32p, f32p, f32p, f32p, i32, i32, C.c_double, C.c_double, f32p, f32p, vp]
-    L.mjl_obs_normalize.argtypes = [f32p, f32p, f32p, i32, i32, C.c_float, f32p, vp]
-    L.mjl_policy_head.argtypes = [f32p, f32p, f32p, i32, i32, f32p, f32p, vp]
-    L.mjl_policy_param_floats.argtypes = [i32, C.POINTER(i32)]
-    L.mjl_policy_param_floats.restype = C.c_longlong
-    L.mjl_policy_fwd.argtypes = [f32p, f32p, f32p, C.c_float, f32p, i32, C.POINTER(i32), f32p, f32p, i32, f32p, f32p, vp]
-    L.mjl_colsum_scratch.argtypes = [i32, i32]
-    L.mjl_colsum_scratch.restype = C.c_longlong
-    L.mjl_colsum.argtypes = [f32p, i32, i32, f32p, f32p, vp]
-    L.mjl_tanh_bwd_colsum.argtypes = [f32p, f32p, i32, i32, f32p, f32p, f32p, vp]
-    L.mjl_slice_sum.argtypes = [f32p, i32, C.c_longlong, f32p, vp]
-    L.mjl_tanh_inplace.argtypes = [f32p, C.c_longlong, vp]
-    L.mjl_colsum_batched_scratch.argtypes = [i32, i32, i32]
-    L.mjl_colsum_batched_scratch.restype = C.c_longlong
-    L.mjl_colsum_batched.argtypes = [f32p, i32, i32, i32, f32p, f32p, vp]
-    L.mjl_tanh_bwd_colsum_batched.argtypes = [f32p, f32p, i32, i32, i32, f32p, f32p, f32p, vp]
-    L.mjl_slice_sum_batched.argtypes = [f32p, i32, i32, C.c_longlong, f32p, vp]
-    L.mjl_mse_strided.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp]
-    L.mjl_bias_act.argtypes = [vp, vp, i32, C.c_longlong, i32, C.c_uint, vp]
-    L.mjl_adam_multi.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, vp, C.c_float, C.c_float, C.c_float, C.c_float,
-                                 vp, vp, i32, vp]
-    L.mjl_ppo_surrogate_clipped.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_float,
-                                            C.c_float, vp, vp, vp, vp, vp]
-    L.mjl_gather_rows_indexed.argtypes = [vp, vp, i32, C.c_longlong, i32, vp, vp, vp, vp]
-    L.mjl_slice_sum_multi.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mjl_twin_loss_head_blocks.argtypes = [i32]
-    L.mjl_twin_loss_head_blocks.restype = C.c_longlong
-    L.mjl_twin_loss_head.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_float,
-                                     C.c_float, vp, vp, vp, vp, vp, vp, vp]
-    L.mjl_twin_fused_shapes.argtypes = [i32, i32, i32]
-    L.mjl_twin_gather_in.argtypes = [vp, vp, i32, C.c_longlong, i32, i32, i32] + [vp] * 13 + [vp]
-    L.mjl_twin_head_bwd.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
-    L.mjl_twin_head_blocks.argtypes = [i32]
-    L.mjl_twin_head_blocks.restype = C.c_longlong
-    L.mjl_twin_head.argtypes = ([vp] * 11 + [i32, i32, i32] + [C.c_float] * 4 + [vp] * 7 + [vp])
-    L.mjl_tanh_bwd_colsum_partials.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    L.mjl_small_mlp_fwd.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp]
-    L.mjl_small_mlp_bwd_input.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp]
-    L.mjl_apg_obs_policy_fwd.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
-    L.mjl_apg_policy_bwd_obs_vjp.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
-    L.mjl_step_vjp.argtypes = [vp, f32p, f32p, f32p, f32p, f32p, vp]
-    L.mjl_env_step_vjp.argtypes = [vp, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, vp]
-    L.mjl_step_vjp_full.argtypes = [vp] + [f32p] * 7 + [vp]
-    L.mjl_env_step_vjp_full.argtypes = [vp] + [f32p] * 12 + [vp]
+    for ret, name, args in HEADER.protos:
+        fn = getattr(L, name)
+        fn.restype = _RETURNS[ret] if ret in _RETURNS else _ctype(ret)
+        fn.argtypes = [_ctype(a) for a in args]
     _lib = L
     return L
 
 
 def check(rc: int):
     if rc != 0:
-        raise MjlError(f"mjx355 error {rc}: {lib().mjl_last_error().decode()}")
+        raise MjlError(f"mjx355 error {rc} ({_ERRORS.get(rc, 'unknown code')}): {lib().mjl_last_error().decode()}")

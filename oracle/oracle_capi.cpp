@@ -1,4 +1,5 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY (see physics.hpp header). C entry points for ctypes.
+#include <cstddef>
 #include <cstdint>
 
 #include "env.hpp"
@@ -27,6 +28,8 @@ int orc_version(void) { return 1; }
 int orc_state_size(void) { return (int)sizeof(orcState); }
 int orc_desc_size(void) { return (int)sizeof(mjlModelDesc); }
 int orc_envcfg_size(void) { return (int)sizeof(mjlEnvConfig); }
+int orc_desc_last_offset(void) { return (int)offsetof(mjlModelDesc, sensor_adr); }
+int orc_envcfg_last_offset(void) { return (int)offsetof(mjlEnvConfig, obs_sign); }
 
 }  // extern "C"
 
