@@ -584,6 +584,63 @@ int mjl_adam_multi(int nt, float* const* p, const float* const* g, float* const*
                    const long long* numel, const int* group, int ngroups, const float* lr, float beta1, float beta2,
                    float eps, float gscale, float* const* step, int* ctr, int advanced, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Batched ray-cast renderer: RGB / depth / segmentation frames from qpos. Replaces the
+ * mujoco.Renderer loop of src/rendering.py:181-192 (mj_forward + update_scene + render per frame)
+ * and serves per-env camera images of a batch. Planes, spheres and capsules have closed-form ray
+ * intersections, so there is no GL and no mesh pipeline; the shading model is DESIGN.md "Rendering".
+ *
+ * mjlVisualDesc is what the MJCF compiler keeps beside mjlModelDesc (mjx_amd/mjcf.py, `visual`):
+ *   geom_rgba               per-geom colour (alpha is carried, not rendered)
+ *   checker_*               the plane geom with a builtin checker texture (checker_geom, -1 = none): its two
+ *                           colours, the world-space cell size along the plane's x / y, and those two axes in
+ *                           the frame of the geom's body
+ *   sky_rgb1 / sky_rgb2     a miss takes (1 - s) rgb2 + s rgb1 with s = (1 + d_z) / 2 of the ray direction d
+ *   light_*                 the one light, frozen in the world at qpos0: position, or direction when
+ *                           light_directional; diffuse colour; ambient term
+ *   znear, zfar             hits are kept for ray parameters in [znear, zfar] (metres)
+ *   cam_*                   ncam <= MJL_MAXCAM cameras: body, MJL_CAM_* mode (any other value: the camera
+ *                           cannot be selected), vertical field of view in degrees; cam_pos / cam_mat the pose in
+ *                           the body's frame (fixed cameras); cam_pos0 / cam_mat0 the world offset from the body's
+ *                           position (track) or subtree centre of mass (trackcom) and the world rotation, both
+ *                           at qpos0 (MuJoCo's cam_pos0 / cam_poscom0 / cam_mat0). Rotations are row-major with
+ *                           the camera's x (right), y (up), z axes as columns; the camera looks along -z.
+ * ------------------------------------------------------------------------------------------- */
+#define MJL_MAXCAM 8
+enum { MJL_CAM_FIXED = 0, MJL_CAM_TRACK = 1, MJL_CAM_TRACKCOM = 2 };
+enum { MJL_RENDER_SHADOWS = 1 };
+
+typedef struct mjlVisualDesc {
+  int32_t ncam, checker_geom, light_directional;
+  float geom_rgba[MJL_MAXGEOM][4];
+  float checker_rgb1[3], checker_rgb2[3], checker_cell[2], checker_xaxis[3], checker_yaxis[3];
+  float sky_rgb1[3], sky_rgb2[3];
+  float light_pos[3], light_dir[3], light_diffuse[3], light_ambient[3];
+  float znear, zfar;
+  int32_t cam_body[MJL_MAXCAM], cam_mode[MJL_MAXCAM];
+  float cam_fovy[MJL_MAXCAM];
+  float cam_pos[MJL_MAXCAM][3], cam_mat[MJL_MAXCAM][9], cam_pos0[MJL_MAXCAM][3], cam_mat0[MJL_MAXCAM][9];
+} mjlVisualDesc;
+
+typedef struct mjlRenderer mjlRenderer;
+
+/* A renderer for `model` on `device`: uploads the model and visual constants and allocates the
+ * per-frame scene scratch for up to max_frames (1..65535) frames per call. MJL_ERR_UNSUPPORTED for a
+ * geom type other than plane, sphere or capsule. The model may be destroyed afterwards. */
+int mjl_renderer_create(const mjlModel* model, const mjlVisualDesc* visual, int max_frames, int device,
+                        mjlRenderer** out);
+void mjl_renderer_destroy(mjlRenderer* renderer);
+/* Render n <= max_frames frames through camera `camera` at width x height pixels, two launches on
+ * `stream`, no allocation and no synchronisation. qpos: device float32 [n, nq] (any buffer: a qpos
+ * history, or a batch's MJL_FIELD_QPOS rows); forward kinematics only, no batch and no constraint
+ * solve. rgb uint8 [n, height, width, 3]; depth float32 [n, height, width], the distance along the
+ * pixel's ray, +inf where nothing lies within zfar; seg int32 [n, height, width], the geom id, -1 =
+ * background. Each output may be NULL, not all three. flags: MJL_RENDER_SHADOWS adds hard shadows.
+ * MJL_ERR_ARG for n > max_frames, a non-positive size, a camera outside the visual description's
+ * cameras or all outputs NULL; MJL_ERR_UNSUPPORTED for a camera whose mode is not an MJL_CAM_* one. */
+int mjl_render_qpos(mjlRenderer* renderer, const float* qpos, int n, int camera, int width, int height, int flags,
+                    uint8_t* rgb, float* depth, int32_t* seg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

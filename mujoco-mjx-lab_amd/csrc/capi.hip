@@ -16,6 +16,7 @@
 #include "apg_kernels.hip"
 #include "ppo_loss_kernels.hip"
 #include "twin_kernels.hip"
+#include "render_kernels.hip"
 
 using namespace mjl;
 
@@ -1681,6 +1682,111 @@ extern "C" int mjl_adam_multi(int nt, float* const* p, const float* const* g, fl
   if (!advanced)
     hipLaunchKernelGGL(step_counters_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step[0],
                        ngroups > 1 ? step[1] : nullptr, ctr);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// renderer (render_kernels.hip)
+// ---------------------------------------------------------------------------------------------
+struct mjlRenderer {
+  int device, max_frames, nq;
+  mjlVisualDesc vis;
+  ModelF* d_model;
+  RenderConst* d_rc;
+  float* d_scene;  // [max_frames, kSceneFloats]
+};
+
+extern "C" int mjl_renderer_create(const mjlModel* model, const mjlVisualDesc* vis, int max_frames, int device,
+                                   mjlRenderer** out) {
+  if (!model || !vis || !out) return fail(MJL_ERR_ARG, "bad argument");
+  *out = nullptr;
+  const mjlModelDesc& d = model->desc;
+  for (int g = 0; g < d.ngeom; g++)
+    if (d.geom_type[g] != MJL_GEOM_PLANE && d.geom_type[g] != MJL_GEOM_SPHERE && d.geom_type[g] != MJL_GEOM_CAPSULE)
+      return fail(MJL_ERR_UNSUPPORTED, "renderer: geom %d has type %d (plane, sphere and capsule are drawn)", g,
+                  d.geom_type[g]);
+  if (max_frames < 1 || max_frames > 65535) return fail(MJL_ERR_ARG, "renderer: max_frames must be in 1..65535");
+  if (vis->ncam < 0 || vis->ncam > MJL_MAXCAM || vis->checker_geom >= d.ngeom || !(vis->zfar > vis->znear) ||
+      !(vis->znear > 0.f))
+    return fail(MJL_ERR_ARG, "renderer: bad visual description");
+  for (int c = 0; c < vis->ncam; c++)
+    if (vis->cam_body[c] < 0 || vis->cam_body[c] >= d.nbody)
+      return fail(MJL_ERR_ARG, "renderer: camera %d is on body %d", c, vis->cam_body[c]);
+  if (vis->checker_geom >= 0 && (!(vis->checker_cell[0] > 0.f) || !(vis->checker_cell[1] > 0.f)))
+    return fail(MJL_ERR_ARG, "renderer: checker cell size must be positive");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MJL_ERR_NOGPU, "no HIP device available");
+  if (device < 0 || device >= ndev) return fail(MJL_ERR_ARG, "device %d out of range", device);
+  HIPCHK(hipSetDevice(device));
+  mjlRenderer* R = new (std::nothrow) mjlRenderer();
+  if (!R) return fail(MJL_ERR_ARG, "out of host memory");
+  std::memset(R, 0, sizeof(*R));
+  R->device = device; R->max_frames = max_frames; R->nq = d.nq; R->vis = *vis;
+  RenderConst rc;
+  std::memset(&rc, 0, sizeof(rc));
+  rc.ngeom = d.ngeom; rc.checker_geom = vis->checker_geom < 0 ? -1 : vis->checker_geom;
+  rc.light_directional = vis->light_directional != 0;
+  for (int g = 0; g < d.ngeom; g++)
+    for (int i = 0; i < 4; i++) rc.geom_rgb[g][i] = vis->geom_rgba[g][i];
+  for (int i = 0; i < 3; i++) {
+    rc.chk_rgb1[i] = vis->checker_rgb1[i]; rc.chk_rgb2[i] = vis->checker_rgb2[i];
+    rc.chk_x[i] = vis->checker_xaxis[i]; rc.chk_y[i] = vis->checker_yaxis[i];
+    rc.sky1[i] = vis->sky_rgb1[i]; rc.sky2[i] = vis->sky_rgb2[i];
+    rc.light_pos[i] = vis->light_pos[i]; rc.light_dir[i] = vis->light_dir[i];
+    rc.diffuse[i] = vis->light_diffuse[i]; rc.ambient[i] = vis->light_ambient[i];
+  }
+  if (rc.checker_geom >= 0) {
+    rc.chk_inv_cell[0] = 1.f / vis->checker_cell[0]; rc.chk_inv_cell[1] = 1.f / vis->checker_cell[1];
+  }
+  rc.znear = vis->znear; rc.zfar = vis->zfar;
+  hipError_t e = hipMalloc(&R->d_model, sizeof(ModelF));
+  if (e == hipSuccess) e = hipMemcpy(R->d_model, &model->mf, sizeof(ModelF), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc(&R->d_rc, sizeof(RenderConst));
+  if (e == hipSuccess) e = hipMemcpy(R->d_rc, &rc, sizeof(RenderConst), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc(&R->d_scene, (size_t)max_frames * kSceneFloats * sizeof(float));
+  if (e != hipSuccess) {
+    (void)hipFree(R->d_model); (void)hipFree(R->d_rc); (void)hipFree(R->d_scene);
+    delete R;
+    return fail(MJL_ERR_HIP, "renderer allocation: %s", hipGetErrorString(e));
+  }
+  *out = R;
+  return MJL_OK;
+}
+
+extern "C" void mjl_renderer_destroy(mjlRenderer* R) {
+  if (!R) return;
+  (void)hipSetDevice(R->device);
+  (void)hipFree(R->d_model); (void)hipFree(R->d_rc); (void)hipFree(R->d_scene);
+  delete R;
+}
+
+extern "C" int mjl_render_qpos(mjlRenderer* R, const float* qpos, int n, int camera, int width, int height, int flags,
+                               uint8_t* rgb, float* depth, int32_t* seg, void* stream) {
+  if (!R || !qpos) return fail(MJL_ERR_ARG, "bad argument");
+  if (n < 1 || n > R->max_frames) return fail(MJL_ERR_ARG, "render: %d frames (the renderer holds 1..%d)", n, R->max_frames);
+  if (width < 1 || height < 1 || width > 16384 || height > 16384)
+    return fail(MJL_ERR_ARG, "render: size %d x %d (1..16384 each)", width, height);
+  if (camera < 0 || camera >= R->vis.ncam) return fail(MJL_ERR_ARG, "render: camera %d of %d", camera, R->vis.ncam);
+  if (!rgb && !depth && !seg) return fail(MJL_ERR_ARG, "render: no output requested");
+  const mjlVisualDesc& v = R->vis;
+  const int mode = v.cam_mode[camera];
+  if (mode != MJL_CAM_FIXED && mode != MJL_CAM_TRACK && mode != MJL_CAM_TRACKCOM)
+    return fail(MJL_ERR_UNSUPPORTED, "render: camera %d has an unsupported mode", camera);
+  if (!(v.cam_fovy[camera] > 0.f && v.cam_fovy[camera] < 180.f))
+    return fail(MJL_ERR_ARG, "render: camera %d has fovy %g", camera, (double)v.cam_fovy[camera]);
+  RenderCam cam;
+  cam.body = v.cam_body[camera]; cam.mode = mode;
+  cam.tan_half = (float)std::tan(0.5 * (double)v.cam_fovy[camera] * 3.14159265358979323846 / 180.0);
+  const bool fixed = mode == MJL_CAM_FIXED;
+  for (int i = 0; i < 3; i++) cam.pos[i] = fixed ? v.cam_pos[camera][i] : v.cam_pos0[camera][i];
+  for (int i = 0; i < 9; i++) cam.mat[i] = fixed ? v.cam_mat[camera][i] : v.cam_mat0[camera][i];
+  const int tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
+  hipLaunchKernelGGL(render_setup_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, R->d_model, R->d_rc, cam,
+                     qpos, R->d_scene);
+  hipLaunchKernelGGL(render_rays_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)n), dim3(256), 0,
+                     (hipStream_t)stream, R->d_rc, R->d_scene, cam.tan_half, width, height, tiles_x,
+                     (flags & MJL_RENDER_SHADOWS) != 0, rgb, depth, seg);
   HIPCHK(hipGetLastError());
   return MJL_OK;
 }

@@ -20,10 +20,11 @@ CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 # every symbol include/mjx355.h declares, in header order
 EXPORTS = [name for _, name, _ in HEADER.protos]
 
-# C type of the header -> ctypes: the two structs and the handle outputs are typed, every other pointer
+# C type of the header -> ctypes: the structs and the handle outputs are typed, every other pointer
 # (buffers, pointer tables, `void* stream`) is an address, scalars are SCALARS
 _TYPED = {"mjlModelDesc*": C.POINTER(abi.ModelDesc), "mjlEnvConfig*": C.POINTER(abi.EnvConfigC),
-          "mjlModel**": C.POINTER(C.c_void_p), "mjlBatch**": C.POINTER(C.c_void_p)}
+          "mjlVisualDesc*": C.POINTER(abi.VisualDesc), "mjlModel**": C.POINTER(C.c_void_p),
+          "mjlBatch**": C.POINTER(C.c_void_p), "mjlRenderer**": C.POINTER(C.c_void_p)}
 _RETURNS = {"void": None, "char*": C.c_char_p}
 _ERRORS = {v: k for k, v in HEADER.enums.items() if k.startswith("MJL_ERR_")}
 

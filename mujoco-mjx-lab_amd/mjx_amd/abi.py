@@ -1,7 +1,7 @@
 """The C ABI's constants and structs as ctypes, and conversion from compiled models.
 
 Nothing here is declared twice: the capacities, `AUX_DIM`, the `OPT_*` and `FIELD` numbers and the
-fields of `ModelDesc` / `EnvConfigC` are read from include/mjx355.h (`_header.py`), the header the
+fields of `ModelDesc` / `EnvConfigC` / `VisualDesc` are read from include/mjx355.h (`_header.py`), the header the
 library is built from and stamped with. `tests/test_abi.py` checks the layouts against a C compiler.
 """
 from __future__ import annotations
@@ -43,6 +43,14 @@ class EnvConfigC(C.Structure):
     _fields_ = _fields("mjlEnvConfig")
 
 
+class VisualDesc(C.Structure):
+    _fields_ = _fields("mjlVisualDesc")
+
+
+CAM_MODE = {k[8:].lower(): v for k, v in _E.items() if k.startswith("MJL_CAM_")}  # "fixed": MJL_CAM_FIXED, ...
+RENDER_SHADOWS = _E["MJL_RENDER_SHADOWS"]
+
+
 _PY = {C.c_int32: int, C.c_float: float, C.c_double: float}  # what a scalar field is set through
 _CAP = {n: _D["MJL_MAX" + c] for n, c in (
     ("nbody", "BODY"), ("njnt", "JNT"), ("nv", "V"), ("nq", "Q"), ("ngeom", "GEOM"), ("npair", "PAIR"),
@@ -80,6 +88,40 @@ def _fill(carr, arr):
             row = carr[i]
             for j in range(arr.shape[1]):
                 row[j] = arr[i, j].item()
+
+
+def visual_desc(m) -> VisualDesc:
+    """Pack a CompiledModel's visual description (mjcf._compile_visual) into the C descriptor. A camera the
+    renderer cannot take (mjcf.camera_id raises for it) keeps its slot with mode -1."""
+    v = m.visual
+    if v is None:
+        raise UnsupportedModel("model has no visual description (compile it from MJCF)")
+    if len(v["cameras"]) > MAXCAM:
+        raise UnsupportedModel(f"model has {len(v['cameras'])} cameras (MJL_MAXCAM = {MAXCAM})")
+    d = VisualDesc()
+    d.ncam = len(v["cameras"])
+    _fill(d.geom_rgba, np.asarray(v["geom_rgba"], float).reshape(-1, 4))
+    ck = v["checker"]
+    d.checker_geom = -1 if ck is None else int(ck["geom"])
+    if ck is not None:
+        for name in ("rgb1", "rgb2", "cell", "xaxis", "yaxis"):
+            _fill(getattr(d, "checker_" + name), np.asarray(ck[name], float))
+    _fill(d.sky_rgb1, np.asarray(v["sky"]["rgb1"], float))
+    _fill(d.sky_rgb2, np.asarray(v["sky"]["rgb2"], float))
+    d.light_directional = int(v["light"]["directional"])
+    for name in ("pos", "dir", "diffuse", "ambient"):
+        _fill(getattr(d, "light_" + name), np.asarray(v["light"][name], float))
+    d.znear, d.zfar = float(v["znear"]), float(v["zfar"])
+    for i, c in enumerate(v["cameras"]):
+        d.cam_body[i] = int(c["body"])
+        d.cam_mode[i] = -1 if c["error"] else CAM_MODE[c["mode"]]
+        d.cam_fovy[i] = float(c["fovy"])
+        pos0 = c["pos0_trackcom"] if c["mode"] == "trackcom" else c["pos0_track"]
+        for k in range(3):
+            d.cam_pos[i][k], d.cam_pos0[i][k] = float(c["pos"][k]), float(pos0[k])
+        for k in range(9):
+            d.cam_mat[i][k], d.cam_mat0[i][k] = float(c["mat"][k]), float(c["mat0"][k])
+    return d
 
 
 def desc_size() -> int:

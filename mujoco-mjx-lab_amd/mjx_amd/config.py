@@ -61,9 +61,12 @@ class BaseConfig:
     log_interval: int = 10
     eval_interval: int = 50
     results_dir: str = "results"
-    save_video: bool = False  # a qpos-history .npz per eval for offline rendering (mjx_amd/rendering.py)
+    save_video: bool = False  # a qpos-history .npz and a rendered .gif per eval (mjx_amd/rendering.py)
     render_fps: int = 60
     render_duration: float = 6.0
+    render_width: int = 640   # src/rendering.py:66-68
+    render_height: int = 480
+    render_camera: str = "side_view"
     camera_name: str = "side_view"
 
 

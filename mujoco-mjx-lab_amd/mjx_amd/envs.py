@@ -172,6 +172,15 @@ class HumanoidEnv:
     def aux(self) -> torch.Tensor:
         return self.data.get("aux")
 
+    def render(self, camera="side_view", width: int = 64, height: int = 64, shadows: bool = True, rgb: bool = True,
+               depth: bool = False, seg: bool = False):
+        """Per-env camera images of the batch's current qpos, [num_envs, H, W, .] each (render.Frames): the
+        pixel-observation entry. Forward kinematics only; the batch is not touched."""
+        if getattr(self, "_renderer", None) is None:
+            from .render import Renderer
+            self._renderer = Renderer(self.sys, self.num_envs, self.data.device.index or 0)
+        return self._renderer.render(self.data.get("qpos"), camera, width, height, shadows, rgb, depth, seg)
+
 
 class EnvState(NamedTuple):
     """The `(mjx.Data, aux)` pair v_reset / v_step pass around (src/envs.py:200,490). `data` is the

@@ -153,6 +153,9 @@ class CompiledModel:
     meaninertia: float = 1.0
     arrays: Dict[str, np.ndarray] = field(default_factory=dict)
     names: Dict[str, List[str]] = field(default_factory=dict)
+    # what the renderer draws with (`_compile_visual`): plain lists and numbers, kept beside the arrays and
+    # out of to_json_dict (the compiled assets carry it in a sibling <name>_visual.json)
+    visual: Optional[dict] = None
 
     def __getattr__(self, k):  # convenient access m.body_mass etc.
         arrays = self.__dict__.get("arrays")
@@ -360,6 +363,7 @@ def compile_xml_string(text: str, name_hint: str = "", sha: str = "") -> Compile
     geoms = []
     sites = []
     body_names, jnt_names, geom_names, site_names = [], [], [], []
+    geom_vis, cam_els, light_els = [], [], []  # for the visual description (_compile_visual)
 
     def add_body(el, parent, childclass, name):
         bid = len(bodies)
@@ -456,6 +460,7 @@ def compile_xml_string(text: str, name_hint: str = "", sha: str = "") -> Compile
                               "density": dens, "priority": int(a["priority"])})
                 geom_names.append(child.get("name", ""))
                 b["geoms"].append(gid)
+                geom_vis.append((dict(child.attrib), a))
             elif tag == "site":
                 a = defaults.resolve("site", child, cc)
                 stype = _SITE_TYPES.get(a.get("type", "sphere"))
@@ -471,6 +476,7 @@ def compile_xml_string(text: str, name_hint: str = "", sha: str = "") -> Compile
             elif tag in ("camera", "light", "inertial"):
                 if tag == "inertial":
                     raise MJCFError("explicit <inertial> not supported")
+                (cam_els if tag == "camera" else light_els).append((defaults.resolve(tag, child, cc), bid))
             else:
                 raise MJCFError(f"body child <{tag}> not supported")
         return bid
@@ -770,7 +776,164 @@ def compile_xml_string(text: str, name_hint: str = "", sha: str = "") -> Compile
     m.nsensordata = len(sensors)
     m.nkey = len(keys)
     _set_const(m)
+    m.visual = _compile_visual(root, m, geom_vis, cam_els, light_els)
     return m
+
+
+# ----------------------------------------------------------------------------------------------
+# visual description: what the ray-cast renderer draws with (mjlVisualDesc, include/mjx355.h)
+# ----------------------------------------------------------------------------------------------
+CAMERA_MODES = ("fixed", "track", "trackcom")
+
+
+def _local_rotation(a: Dict[str, str]):
+    """Rotation of a camera in its body's frame (columns = its x, y, z axes) from `xyaxes`, `quat` or
+    `zaxis`; (None, reason) for an orientation outside that subset."""
+    if "xyaxes" in a:
+        v = np.array(_floats(a["xyaxes"]))
+        x = v[:3] / np.linalg.norm(v[:3])
+        y = v[3:] - np.dot(v[3:], x) * x  # MuJoCo orthogonalises y against x
+        y = y / np.linalg.norm(y)
+        return np.stack([x, y, np.cross(x, y)], axis=1), ""
+    if "quat" in a:
+        q = np.array(_floats(a["quat"]))
+        return quat2mat(q / np.linalg.norm(q)), ""
+    if "zaxis" in a:
+        return quat2mat(z2quat(_floats(a["zaxis"]))), ""
+    for o in ("euler", "axisangle"):
+        if o in a:
+            return None, f"orientation '{o}' not supported (xyaxes, quat, zaxis are)"
+    return np.eye(3), ""
+
+
+def _compile_visual(root, m: CompiledModel, geom_vis, cam_els, light_els) -> dict:
+    """Colours, the checker plane, the sky, the first light and the cameras, as plain lists.
+
+    geom rgba: the geom's own `rgba`, else its own material's, else its default class's `rgba`, else that
+    class's material's, else MuJoCo's 0.5 0.5 0.5 1. A plane whose material has a `builtin="checker"`
+    texture is the checker plane (the first such geom): its colour is rgb1 / rgb2 by cell parity times
+    the geom rgba. Cell size: MuJoCo's builtin checker image is 2 x 2 cells; with `texuniform` the image
+    spans 1 / texrepeat world units, so a cell is 1 / (2 texrepeat); without it the image is repeated
+    texrepeat times over the plane's 2 size, a cell is size / texrepeat (an infinite plane, size 0, then
+    falls back to the texuniform rule). Planes are drawn infinite. znear / zfar are `<visual><map>`'s
+    values taken as metres (MuJoCo scales them by the model extent), defaults 0.01 and 30. The ambient
+    term is the light's `ambient` plus `<visual><headlight ambient>` (default 0.1); the headlight's own
+    diffuse and every further light are not modelled. Lights are frozen in the world at qpos0
+    (`targetbody` / `targetbodycom` aim, `track` / `trackcom` pose); spot cutoff and attenuation are
+    ignored. Cameras with a mode or orientation outside the supported subset are kept with an `error`
+    that `camera_id` raises when that camera is selected."""
+    A = m.arrays
+    kin = _fk_and_mass(m, A["qpos0"])
+    asset = root.find("asset")
+    textures, materials, sky = {}, {}, None
+    for el in (asset if asset is not None else []):
+        if el.tag == "texture":
+            if el.get("type", "cube") == "skybox" and sky is None:
+                sky = el
+            if "name" in el.attrib:
+                textures[el.get("name")] = el
+        elif el.tag == "material":
+            materials[el.get("name")] = el
+
+    def mat_rgba(name):
+        if name not in materials:
+            raise MJCFError(f"unknown material '{name}'")
+        return _floats(materials[name].get("rgba", "1 1 1 1"))
+
+    rgba, checker = [], None
+    for g, (own, a) in enumerate(geom_vis):
+        if "rgba" in own:
+            c = _floats(own["rgba"])
+        elif "material" in own:
+            c = mat_rgba(own["material"])
+        elif "rgba" in a:
+            c = _floats(a["rgba"])
+        elif "material" in a:
+            c = mat_rgba(a["material"])
+        else:
+            c = [0.5, 0.5, 0.5, 1.0]
+        rgba.append([float(x) for x in c])
+        mat = materials.get(a.get("material", ""))
+        tex = textures.get(mat.get("texture", "")) if mat is not None else None
+        if (checker is None and tex is not None and tex.get("builtin") == "checker"
+                and A["geom_type"][g] == GEOM_PLANE):
+            rep = (_floats(mat.get("texrepeat", "1 1")) * 2)[:2]
+            size = A["geom_size"][g]
+            if mat.get("texuniform", "false") == "true":
+                cell = [1.0 / (2.0 * r) for r in rep]
+            else:
+                cell = [float(size[i]) / rep[i] if size[i] > 0 else 1.0 / (2.0 * rep[i]) for i in range(2)]
+            R = quat2mat(A["geom_quat"][g])
+            checker = {"geom": g, "rgb1": _floats(tex.get("rgb1", "0.8 0.8 0.8")),
+                       "rgb2": _floats(tex.get("rgb2", "0.5 0.5 0.5")), "cell": cell,
+                       "xaxis": R[:, 0].tolist(), "yaxis": R[:, 1].tolist()}
+
+    if sky is not None:
+        rgb1 = _floats(sky.get("rgb1", "0.8 0.8 0.8"))
+        rgb2 = _floats(sky.get("rgb2", "0.5 0.5 0.5")) if sky.get("builtin") == "gradient" else rgb1
+    else:
+        rgb1 = rgb2 = [0.0, 0.0, 0.0]
+
+    vis_el = root.find("visual")
+    vmap = vis_el.find("map") if vis_el is not None else None
+    head = vis_el.find("headlight") if vis_el is not None else None
+    znear = float(vmap.get("znear", 0.01)) if vmap is not None else 0.01
+    zfar = float(vmap.get("zfar", 30.0)) if vmap is not None else 30.0
+    ambient = np.array(_floats(head.get("ambient", "0.1 0.1 0.1")) if head is not None else [0.1, 0.1, 0.1])
+
+    light = {"directional": 0, "pos": [0.0, 0.0, 10.0], "dir": [0.0, 0.0, -1.0], "diffuse": [0.7, 0.7, 0.7],
+             "ambient": ambient.tolist()}
+    if light_els:
+        a, b = light_els[0]
+        pos = kin["xpos"][b] + kin["xmat"][b] @ np.array(_floats(a.get("pos", "0 0 0")))
+        d = kin["xmat"][b] @ np.array(_floats(a.get("dir", "0 0 -1")))
+        mode = a.get("mode", "fixed")
+        if mode in ("targetbody", "targetbodycom"):
+            t = m.name2id("body", a.get("target", ""))
+            if t < 0:
+                raise MJCFError(f"light target body '{a.get('target')}' not found")
+            d = (kin["xpos"][t] if mode == "targetbody" else kin["subtree_com"][t]) - pos
+        d = d / max(np.linalg.norm(d), mjMINVAL)
+        light = {"directional": int(a.get("directional", "false") == "true"), "pos": pos.tolist(), "dir": d.tolist(),
+                 "diffuse": _floats(a.get("diffuse", "0.7 0.7 0.7")),
+                 "ambient": (ambient + np.array(_floats(a.get("ambient", "0 0 0")))).tolist()}
+
+    cameras = []
+    for a, b in cam_els:
+        R, err = _local_rotation(a)
+        mode = a.get("mode", "fixed")
+        if mode not in CAMERA_MODES:
+            err = f"mode '{mode}' not supported ({', '.join(CAMERA_MODES)} are)"
+        R = np.eye(3) if R is None else R
+        pos = np.array(_floats(a.get("pos", "0 0 0")))
+        pos_w = kin["xpos"][b] + kin["xmat"][b] @ pos
+        cameras.append({"name": a.get("name", ""), "body": int(b), "mode": mode, "fovy": float(a.get("fovy", 45.0)),
+                        "pos": pos.tolist(), "mat": R.ravel().tolist(),
+                        "mat0": (kin["xmat"][b] @ R).ravel().tolist(),
+                        "pos0_track": (pos_w - kin["xpos"][b]).tolist(),
+                        "pos0_trackcom": (pos_w - kin["subtree_com"][b]).tolist(), "error": err})
+    return {"geom_rgba": rgba, "checker": checker, "sky": {"rgb1": rgb1, "rgb2": rgb2}, "light": light,
+            "cameras": cameras, "znear": znear, "zfar": zfar}
+
+
+def camera_id(m: CompiledModel, camera) -> int:
+    """Index of a camera given by name or index; MJCFError (naming the camera) for one the renderer cannot
+    take, or one the model does not have."""
+    if m.visual is None:
+        raise MJCFError("model has no visual description (compile it from MJCF)")
+    cams = m.visual["cameras"]
+    if isinstance(camera, str):
+        ids = [i for i, c in enumerate(cams) if c["name"] == camera]
+        if not ids:
+            raise MJCFError(f"camera '{camera}' not found (model has: {', '.join(c['name'] for c in cams)})")
+        cid = ids[0]
+    else:
+        cid = int(camera)
+        if not 0 <= cid < len(cams):
+            raise MJCFError(f"camera index {cid} out of range (model has {len(cams)})")
+    if cams[cid]["error"]:
+        raise MJCFError(f"camera '{cams[cid]['name']}': {cams[cid]['error']}")
+    return cid
 
 
 # ----------------------------------------------------------------------------------------------
@@ -925,6 +1088,12 @@ def load_model(path: str) -> CompiledModel:
     """Load an MJCF `.xml` (compiled here) or a pre-compiled `.json` model."""
     if path.endswith(".json"):
         import json
+        import os
         with open(path) as f:
-            return CompiledModel.from_json_dict(json.load(f))
+            m = CompiledModel.from_json_dict(json.load(f))
+        vpath = path[:-len(".json")] + "_visual.json"  # the visual description travels beside the arrays
+        if os.path.exists(vpath):
+            with open(vpath) as f:
+                m.visual = json.load(f)
+        return m
     return compile_xml(path)

@@ -1460,7 +1460,9 @@ class PPOTrainer:
     def dump_qpos_history(self, it: int) -> Optional[str]:
         """train_ppo.py:433-456 render_video (save_video): one env, deterministic mean action of the
         normalised obs for render_duration seconds, reset to its initial state when done; the qpos
-        history goes to <training_dir>/videos/iter_<it+1:06d>.npz (mjx_amd/rendering.py)."""
+        history goes to <training_dir>/videos/iter_<it+1:06d>.npz and, rendered through render_camera at
+        render_width x render_height with the reference's frame stride, to iter_<it+1:06d>.gif beside it
+        (mjx_amd/rendering.py). Returns the .npz path."""
         if not self.out_dir or self.eval_env is None or not hasattr(self.eval_env, "get_state"):
             return None
         from . import rendering
@@ -1472,9 +1474,17 @@ class PPOTrainer:
         pol = lambda o: self.policy(self.rms.normalize(o))[0]  # noqa: E731
         qpos, act = rendering.rollout_qpos_history(self._render_env, pol, float(self.cfg.render_duration))
         path = os.path.join(self.out_dir, "videos", f"iter_{it + 1:06d}.npz")
-        return rendering.save_qpos_history(path, qpos[:, 0], act[:, 0], float(self._render_env.sys.m.timestep),
-                                           int(self.cfg.render_fps), os.path.basename(str(self.cfg.xml_path)),
-                                           str(self.cfg.camera_name))
+        dt, fps = float(self._render_env.sys.m.timestep), int(self.cfg.render_fps)
+        path = rendering.save_qpos_history(path, qpos[:, 0], act[:, 0], dt, fps,
+                                           os.path.basename(str(self.cfg.xml_path)), str(self.cfg.camera_name))
+        if getattr(self, "_renderer", None) is None:
+            from .render import Renderer
+            self._renderer = Renderer(self._render_env.sys, 64, self.device.index or 0)
+        frames = rendering.render_qpos_history(self._renderer, qpos[:, 0], rendering.frame_stride(dt, fps),
+                                               str(self.cfg.render_camera), int(self.cfg.render_width),
+                                               int(self.cfg.render_height))
+        rendering.save_video(os.path.splitext(path)[0] + ".gif", frames, fps)
+        return path
 
     def save_checkpoint(self, it: int, metrics: dict):
         """checkpoint_utils.py:38-61 layout (results/<ts>_ppo/checkpoints/), torch state dicts."""

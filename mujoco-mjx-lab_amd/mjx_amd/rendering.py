@@ -1,10 +1,12 @@
-"""qpos-history dump of a policy rollout, for offline rendering (reference src/rendering.py:57-195).
+"""Policy-rollout videos (reference src/rendering.py:57-195): the qpos history, its frames, the file.
 
 The reference scans `duration / dt` env steps of a deterministic policy on one env, resetting to the
 rollout's own initial state whenever the env is done, collects `qpos` after every step and renders
-the history with mujoco.Renderer (every `1 / (fps dt)`-th frame). Rendering is out of scope here
-(no mujoco / GL on the box); the history is written as an `.npz` that any MuJoCo install renders
-offline with the reference's own loop (`mj_data.qpos[:] = qpos[i]; mj_forward; renderer.render()`):
+the history with mujoco.Renderer (every `1 / (fps dt)`-th frame). Here `rollout_qpos_history` is that
+scan, `render_qpos_history` renders the strided history with the ray-cast renderer (render.py; no
+mujoco, no GL) and `save_video` writes the frames as an animated GIF. The history is also written as
+an `.npz`, which any MuJoCo install renders offline with the reference's own loop
+(`mj_data.qpos[:] = qpos[i]; mj_forward; renderer.render()`):
 
     qpos [T, nq]   post-step (post-reset-merge) qpos, as the reference's scan returns it
     act  [T, nu]   the clipped actions that produced it (replayable through the env)
@@ -55,7 +57,7 @@ def save_qpos_history(path: str, qpos: np.ndarray, act: np.ndarray, dt: float, f
     """Write the history (one env: [T, nq]) next to where the reference writes its video
     (training_dir/videos/<prefix>_<step+1:06d>.npz instead of .mp4, training_utils.py:191-195)."""
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-    stride = max(1, int(1.0 / (fps * dt)))
+    stride = frame_stride(dt, fps)
     np.savez(path, qpos=qpos, act=act, dt=dt, fps=fps, stride=stride, duration=qpos.shape[0] * dt,
              model=model, camera_name=camera_name)
     return path
@@ -65,3 +67,51 @@ def load_qpos_history(path: str) -> dict:
     """Read a dump back (plain arrays, no pickle)."""
     with np.load(path, allow_pickle=False) as f:
         return {k: f[k] for k in f.files}
+
+
+def frame_stride(dt: float, fps: int) -> int:
+    """Every how many steps the reference takes a frame (src/rendering.py:184)."""
+    return max(1, int(1.0 / (fps * dt)))
+
+
+@torch.no_grad()
+def render_qpos_history(renderer, qpos, stride: int = 1, camera="side_view", width: int = 640, height: int = 480,
+                        shadows: bool = True) -> np.ndarray:
+    """Frames uint8 [ceil(T / stride), H, W, 3] of a qpos history [T, nq] (numpy or torch), every
+    `stride`-th step as src/rendering.py:186 takes them, rendered in chunks of the renderer's max_frames."""
+    q = torch.as_tensor(np.asarray(qpos) if not torch.is_tensor(qpos) else qpos)[::stride]
+    out = np.empty((q.shape[0], height, width, 3), np.uint8)
+    for i in range(0, q.shape[0], renderer.max_frames):
+        chunk = q[i:i + renderer.max_frames]
+        out[i:i + chunk.shape[0]] = renderer.render(chunk, camera, width, height, shadows).rgb.cpu().numpy()
+    return out
+
+
+def save_video(path: str, frames: np.ndarray, fps: int = 60) -> str:
+    """Write frames uint8 [T, H, W, 3] as an animated GIF at `path` (frame time rounded to GIF's 10 ms
+    units; each frame quantised to its own palette of up to 256 colours) and return the path written. Without
+    PIL the frames go to `<path minus extension>.npy` instead, and a line on stderr says so."""
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    try:
+        from PIL import Image
+    except ImportError:
+        import sys
+        alt = os.path.splitext(path)[0] + ".npy"
+        np.save(alt, frames)
+        print(f"save_video: PIL is not installed; wrote the raw frames to {alt} instead of {path}", file=sys.stderr)
+        return alt
+    # one palette per frame: the frame's own colours where they fit (exact), else PIL's adaptive quantiser
+    imgs = []
+    for f in frames:
+        key = (f[..., 0].astype(np.uint32) << 16) | (f[..., 1].astype(np.uint32) << 8) | f[..., 2]
+        uniq, inv = np.unique(key, return_inverse=True)
+        if uniq.size <= 256:
+            im = Image.frombytes("P", (f.shape[1], f.shape[0]), inv.astype(np.uint8).tobytes())
+            im.putpalette(np.stack([uniq >> 16, (uniq >> 8) & 255, uniq & 255], axis=1).astype(np.uint8).tobytes())
+        else:
+            im = Image.fromarray(f).quantize(colors=256, dither=Image.Dither.NONE)
+        imgs.append(im)
+    imgs[0].save(path, save_all=True, append_images=imgs[1:], duration=max(10, int(round(1000.0 / fps / 10.0)) * 10),
+                 loop=0, disposal=1, optimize=False)
+    return path

@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--seed", type=int, default=None, help="override the config's seed")
     ap.add_argument("--jax-keys", action="store_true",
                     help="draw env resets from train_ppo.py's jax.random key chain (same reset stream as the reference)")
+    ap.add_argument("--save-video", action="store_true",
+                    help="per eval, write the policy rollout's qpos history (.npz) and its rendered video (.gif)")
     a = ap.parse_args()
 
     cfg = PPOConfig.from_json(a.config) if a.config else reference_ppo_config()
@@ -47,6 +49,8 @@ def main():
         cfg.results_dir = a.results_dir
     if a.seed is not None:
         cfg.seed = a.seed
+    if a.save_video:
+        cfg.save_video = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank, local = int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))

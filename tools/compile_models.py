@@ -21,6 +21,8 @@ def main(src_dir):
         out = os.path.join(ASSETS, name + ".json")
         with open(out, "w") as f:
             json.dump(m.to_json_dict(), f)
+        with open(os.path.join(ASSETS, name + "_visual.json"), "w") as f:  # what the renderer draws with
+            json.dump(m.visual, f, indent=1)
         print(f"{out}: nq={m.nq} nv={m.nv} npair={m.npair} mass={m.body_mass.sum():.4f}")
 
 
