@@ -159,6 +159,8 @@ int mjl_model_create(const mjlModelDesc* desc, mjlModel** out);
 void mjl_model_destroy(mjlModel* model);
 /* Max constraint rows the model can produce (contacts + limits); sizes per-env scratch. */
 int mjl_model_nefc_max(const mjlModel* model);
+/* Max contacts one env can produce (one per candidate pair, two per plane-capsule pair). */
+int mjl_model_ncon_max(const mjlModel* model);
 
 /* Replaces the batched mjx.make_data pytree (src/envs.py:110): owns per-env state on `device`,
  * initialised like make_data (qpos = qpos0, everything else zero). */
@@ -194,6 +196,29 @@ int mjl_set(mjlBatch* batch, int field, const float* src, const float* mask, voi
 /* Replaces mjx.forward (src/envs.py:112): full forward pass, no integration, on envs with
  * mask > 0.5 (mask may be NULL = all). Results readable via mjl_get. */
 int mjl_forward(mjlBatch* batch, const float* mask, void* stream);
+
+/* mjl_forward on envs with mask > 0.5 (NULL = all), then the contacts of that forward pass.
+ * Replaces reading Data.contact and mj_contactForce after mjx.forward.
+ * Per env, contacts c < min(ncon[env], max_con) in the kernel's emission order, which is also the
+ * order of their constraint rows. Entries c >= ncon[env] are filled: geom = -1, the rest 0.
+ * ncon      int32 [nenv]               true count, also when it exceeds max_con; required
+ * geom      int32 [nenv, max_con, 2]   geom1, geom2
+ * dim       int32 [nenv, max_con]      condim (1 or 3)
+ * efc_adr   int32 [nenv, max_con]      first constraint row of the contact
+ * dist      float [nenv, max_con]      signed distance
+ * pos       float [nenv, max_con, 3]   world position
+ * frame     float [nenv, max_con, 9]   rows: normal from geom1 to geom2, tangent 1, tangent 2
+ * force     float [nenv, max_con, 3]   contact-frame force (normal, t1, t2), mj_contactForce:
+ *                                      pyramidal: normal = sum of the rows' forces,
+ *                                      t_i = (f[2i] - f[2i+1]) mu; condim 1: (f, 0, 0)
+ * body_force float [nenv, nbody, 3]    net world-frame contact force on each body: +F on geom2's
+ *                                      body, -F on geom1's (body 0 = world), F = frame^T force,
+ *                                      summed over ALL ncon contacts whatever max_con is, in contact order
+ * Every output but ncon may be NULL. Envs outside the mask keep their output rows untouched.
+ * No allocation, no synchronisation, capturable. MJL_ERR_ARG: null batch / ncon, max_con < 1. */
+int mjl_forward_contacts(mjlBatch* batch, const float* mask, int max_con, int32_t* ncon, int32_t* geom,
+                         int32_t* dim, int32_t* efc_adr, float* dist, float* pos, float* frame, float* force,
+                         float* body_force, void* stream);
 
 /* Replaces mjx.step (src/envs.py:345): ctrl (device [nenv, nu], may be NULL = keep current)
  * -> forward + integrate, state updated in place. */

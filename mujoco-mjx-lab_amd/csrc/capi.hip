@@ -17,6 +17,7 @@
 #include "ppo_loss_kernels.hip"
 #include "twin_kernels.hip"
 #include "render_kernels.hip"
+#include "contact_kernels.hip"
 
 using namespace mjl;
 
@@ -388,6 +389,7 @@ int mjl_model_create(const mjlModelDesc* d, mjlModel** out) {
 
 void mjl_model_destroy(mjlModel* m) { delete m; }
 int mjl_model_nefc_max(const mjlModel* m) { return m ? m->nefc_max : -1; }
+int mjl_model_ncon_max(const mjlModel* m) { return m ? m->ncon_max : -1; }
 
 int mjl_batch_create(const mjlModel* model, int nenv, int device, mjlBatch** out) {
   if (!model || !out || nenv <= 0) return fail(MJL_ERR_ARG, "bad argument");
@@ -660,6 +662,35 @@ int mjl_forward(mjlBatch* B, const float* mask, void* stream) {
   KParams P = make_params(B);
   P.mask = mask;
   return launch<MODE_FORWARD>(B, P, stream);
+}
+
+// Two launches: the forward pass with this call's rows in the global slab (the batch's
+// MJL_OPT_FORCE_GLOBAL_ROWS option is not touched), then the readout of that slab (contact_kernels.hip).
+int mjl_forward_contacts(mjlBatch* B, const float* mask, int max_con, int32_t* ncon, int32_t* geom, int32_t* dim,
+                         int32_t* efc_adr, float* dist, float* pos, float* frame, float* force, float* body_force,
+                         void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (!ncon) return fail(MJL_ERR_ARG, "ncon is required");
+  if (max_con < 1) return fail(MJL_ERR_ARG, "max_con must be >= 1");
+  KParams P = make_params(B);
+  P.mask = mask;
+  P.force_global_rows = 1;
+  if (int rc = launch<MODE_FORWARD>(B, P, stream)) return rc;
+  ContactOut O;
+  O.ncon = ncon; O.geom = geom; O.dim = dim; O.efc_adr = efc_adr;
+  O.dist = dist; O.pos = pos; O.frame = frame; O.force = force; O.body_force = body_force;
+  O.max_con = max_con;
+  dim3 grid(B->nenv), block(64);
+  if (B->model->nvc == 0)
+    hipLaunchKernelGGL(contacts_kernel<DHum>, grid, block, 0, (hipStream_t)stream, (const ModelF*)B->d_model,
+                       (const float*)B->s.stats, mask, B->d_scratch, B->scratch_stride, B->gmax_efc, B->gmax_con,
+                       B->nenv, O);
+  else
+    hipLaunchKernelGGL(contacts_kernel<DGen>, grid, block, 0, (hipStream_t)stream, (const ModelF*)B->d_model,
+                       (const float*)B->s.stats, mask, B->d_scratch, B->scratch_stride, B->gmax_efc, B->gmax_con,
+                       B->nenv, O);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
 }
 
 int mjl_step(mjlBatch* B, const float* ctrl, void* stream) {

@@ -13,6 +13,14 @@ ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets")
 BUILTIN_MODELS = ("humanoid_mjx", "humanoid")
 
 
+def __getattr__(name):
+    # the contact readout of `mjx` (mjl_forward_contacts), resolved on first use: `mjx` imports torch
+    if name in ("Contacts", "forward_contacts"):
+        from . import mjx
+        return getattr(mjx, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def load_model(name_or_path: str) -> CompiledModel:
     """`mujoco.MjModel.from_xml_path` analog. Accepts an MJCF path, a compiled `.json`, or one
     of the built-in names ("humanoid_mjx", "humanoid", also "models/humanoid_mjx.xml" as the

@@ -14,6 +14,7 @@ return it, and fields are read/written as torch tensors on the batch's GPU.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
@@ -54,6 +55,11 @@ class Model:
     @property
     def nefc_max(self) -> int:
         return lib().mjl_model_nefc_max(self._h)
+
+    @property
+    def ncon_max(self) -> int:
+        """Most contacts one env can have: one per candidate pair, two per plane-capsule pair."""
+        return lib().mjl_model_ncon_max(self._h)
 
     def __del__(self):
         try:
@@ -137,6 +143,60 @@ def make_data(sys: Model, nenv: int = 1, device: int = 0) -> Data:
 def forward(sys: Model, d: Data, mask: Optional[torch.Tensor] = None) -> Data:
     check(lib().mjl_forward(d.handle, _ptr(mask), _stream()))
     return d
+
+
+@dataclass
+class Contacts:
+    """Data.contact with a leading env axis, plus mj_contactForce's per-contact forces (forward_contacts).
+    Contact c of env e is valid for c < min(ncon[e], max_con); the entries past ncon[e] (and every entry of
+    an env outside the call's mask) hold geom -1 and zeros. Order: the kernel's emission order, which is
+    the order of the contacts' constraint rows."""
+    ncon: torch.Tensor         # int32 [nenv], the true count (may exceed max_con)
+    geom: torch.Tensor         # int32 [nenv, max_con, 2]: geom1, geom2
+    dim: torch.Tensor          # int32 [nenv, max_con]: condim, 1 or 3
+    efc_address: torch.Tensor  # int32 [nenv, max_con]: the contact's first constraint row
+    dist: torch.Tensor         # [nenv, max_con]
+    pos: torch.Tensor          # [nenv, max_con, 3]
+    frame: torch.Tensor        # [nenv, max_con, 3, 3]: rows = normal (geom1 -> geom2), tangent 1, tangent 2
+    force: torch.Tensor        # [nenv, max_con, 3]: contact-frame force (normal, tangent 1, tangent 2)
+    body_force: Optional[torch.Tensor]  # [nenv, nbody, 3]: net world-frame contact force per body, or None
+
+    def force_world(self) -> torch.Tensor:
+        """frame^T force [nenv, max_con, 3]: the force on geom2's body in the world frame (geom1's gets
+        the opposite)."""
+        return torch.einsum("ecij,eci->ecj", self.frame, self.force)
+
+
+def _iptr(t: torch.Tensor):
+    if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
+        raise MjlError("device index buffers must be contiguous int32 CUDA tensors")
+    return C.c_void_p(t.data_ptr())
+
+
+def forward_contacts(sys: Model, d: Data, mask: Optional[torch.Tensor] = None, max_con: Optional[int] = None,
+                     body_force: bool = False) -> Contacts:
+    """mjx.forward on the envs with mask > 0.5 (None: all), returning that pass's contacts: what the
+    reference reads from Data.contact and mj_contactForce after mjx.forward. max_con (None: sys.ncon_max,
+    which truncates nothing) is the per-env capacity of the returned arrays; ncon and body_force always
+    cover every contact. See include/mjx355.h mjl_forward_contacts."""
+    mc = sys.ncon_max if max_con is None else int(max_con)
+    if mc < 1:
+        raise MjlError("max_con must be >= 1")
+    n, dev = d.nenv, d.device
+    # with a mask the library leaves masked-out rows untouched: pre-fill them with the sentinel
+    def buf(dtype, *shape, fill=0):
+        if mask is None:
+            return torch.empty(shape, dtype=dtype, device=dev)
+        return torch.full(shape, fill, dtype=dtype, device=dev)
+    i32, f32 = torch.int32, torch.float32
+    c = Contacts(ncon=buf(i32, n), geom=buf(i32, n, mc, 2, fill=-1), dim=buf(i32, n, mc), efc_address=buf(i32, n, mc),
+                 dist=buf(f32, n, mc), pos=buf(f32, n, mc, 3), frame=buf(f32, n, mc, 3, 3), force=buf(f32, n, mc, 3),
+                 body_force=buf(f32, n, sys.nbody, 3) if body_force else None)
+    mk = None if mask is None else mask.to(device=dev, dtype=torch.float32).contiguous()
+    check(lib().mjl_forward_contacts(d.handle, _ptr(mk), mc, _iptr(c.ncon), _iptr(c.geom), _iptr(c.dim),
+                                     _iptr(c.efc_address), _ptr(c.dist), _ptr(c.pos), _ptr(c.frame), _ptr(c.force),
+                                     _ptr(c.body_force), _stream()))
+    return c
 
 
 def step(sys: Model, d: Data, ctrl: Optional[torch.Tensor] = None) -> Data:
