@@ -1,5 +1,6 @@
 // mjx355 C ABI (include/mjx355.h): model upload, batch state ownership, kernel launches.
-// Host side only; the kernels live in step_kernels.hip (same translation unit).
+// Host side only; the kernels live in step_kernels.hip (same translation unit), the conversion of a model
+// descriptor into the device's model block in model_host.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -7,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 
@@ -18,6 +20,7 @@
 #include "twin_kernels.hip"
 #include "render_kernels.hip"
 #include "contact_kernels.hip"
+#include "model_host.h"
 
 using namespace mjl;
 
@@ -121,269 +124,17 @@ int mjl_debug_set_stamps(unsigned long long* dev_buf) {
 }
 #endif
 
-static void q2m_host(const double* q, double* m) {
-  double w = q[0], x = q[1], y = q[2], z = q[3];
-  m[0] = 1 - 2 * (y * y + z * z); m[1] = 2 * (x * y - w * z); m[2] = 2 * (x * z + w * y);
-  m[3] = 2 * (x * y + w * z); m[4] = 1 - 2 * (x * x + z * z); m[5] = 2 * (y * z - w * x);
-  m[6] = 2 * (x * z - w * y); m[7] = 2 * (y * z + w * x); m[8] = 1 - 2 * (x * x + y * y);
-}
-
 int mjl_model_create(const mjlModelDesc* d, mjlModel** out) {
   if (!d || !out) return fail(MJL_ERR_ARG, "null argument");
   *out = nullptr;
-  if (d->nbody > MJL_MAXBODY || d->njnt > MJL_MAXJNT || d->nv > MJL_MAXV || d->nq > MJL_MAXQ ||
-      d->ngeom > MJL_MAXGEOM || d->nsite > MJL_MAXSITE || d->nu > MJL_MAXU || d->ntendon > MJL_MAXTENDON ||
-      d->npair > MJL_MAXPAIR || d->nsensor > MJL_MAXSENSOR || d->nbody < 2 || d->nv < 1)
-    return fail(MJL_ERR_UNSUPPORTED, "model sizes exceed kernel capacities");
-  if (d->nq - 7 + d->nv + 2 > 64) return fail(MJL_ERR_UNSUPPORTED, "too many reset draws for one wave");
-  if (d->solver != MJL_SOLVER_NEWTON && d->solver != MJL_SOLVER_CG)
-    return fail(MJL_ERR_UNSUPPORTED, "solver %d not supported (Newton, CG)", d->solver);
-  if (d->integrator != MJL_INT_EULER && d->integrator != MJL_INT_IMPLICITFAST)
-    return fail(MJL_ERR_UNSUPPORTED, "integrator %d not supported (Euler, implicitfast)", d->integrator);
-  mjlModel* M = new (std::nothrow) mjlModel();
+  std::unique_ptr<mjlModel> M(new (std::nothrow) mjlModel());
   if (!M) return fail(MJL_ERR_ARG, "out of host memory");
+  std::string msg;
+  if (int rc = model_build(d, M->mf, M->nefc_max, M->ncon_max, msg)) return fail(rc, "%s", msg.c_str());
   M->desc = *d;
-  ModelF& f = M->mf;
-  std::memset(&f, 0, sizeof(f));
-  f.nq = d->nq; f.nv = d->nv; f.nu = d->nu; f.nbody = d->nbody; f.njnt = d->njnt; f.ngeom = d->ngeom;
-  f.nsite = d->nsite; f.ntendon = d->ntendon; f.npair = d->npair; f.nsensor = d->nsensor;
-  f.nsensordata = d->nsensordata; f.iterations = d->iterations; f.ls_iterations = d->ls_iterations;
-  f.solver = d->solver; f.integrator = d->integrator; f.eulerdamp = d->eulerdamp;
-  f.timestep = (float)d->timestep; f.impratio = (float)d->impratio; f.tolerance = (float)d->tolerance;
-  f.ls_tolerance = (float)d->ls_tolerance; f.meaninertia = (float)d->meaninertia;
-  f.scale = (float)(1.0 / (d->meaninertia * (d->nv > 1 ? d->nv : 1)));
-  for (int i = 0; i < 3; i++) f.gravity[i] = (float)d->gravity[i];
-  int maxlevel = 0;
-  for (int b = 0; b < d->nbody; b++) {
-    f.body_parentid[b] = d->body_parentid[b]; f.body_rootid[b] = d->body_rootid[b];
-    f.body_jntadr[b] = d->body_jntadr[b]; f.body_jntnum[b] = d->body_jntnum[b];
-    f.body_dofadr[b] = d->body_dofadr[b]; f.body_dofnum[b] = d->body_dofnum[b];
-    f.body_subtree_end[b] = d->body_subtree_end[b]; f.body_level[b] = d->body_level[b];
-    if (d->body_level[b] > maxlevel) maxlevel = d->body_level[b];
-    for (int i = 0; i < 3; i++) { f.body_pos[b][i] = (float)d->body_pos[b][i]; f.body_ipos[b][i] = (float)d->body_ipos[b][i]; }
-    for (int i = 0; i < 4; i++) f.body_quat[b][i] = (float)d->body_quat[b][i];
-    for (int i = 0; i < 6; i++) f.body_inertia[b][i] = (float)d->body_inertia[b][i];
-    f.body_mass[b] = (float)d->body_mass[b];
-    f.body_invweight0[b][0] = (float)d->body_invweight0[b][0];
-    f.body_invweight0[b][1] = (float)d->body_invweight0[b][1];
-    if (b > 0 && d->body_parentid[b] >= b) { delete M; return fail(MJL_ERR_ARG, "bodies must be in DFS order"); }
-  }
-  f.maxlevel = maxlevel;
-  for (int b = 1; b < d->nbody; b++)
-    if (d->body_parentid[b] == 0) f.root[f.nroot++] = b;
-  // dof masks along ancestor chains
-  for (int b = 1; b < d->nbody; b++) {
-    uint32_t mask = 0;
-    for (int bb = b; bb > 0; bb = d->body_parentid[bb])
-      for (int k = d->body_dofadr[bb]; k < d->body_dofadr[bb] + d->body_dofnum[bb]; k++) mask |= 1u << k;
-    f.body_dofmask[b] = mask;
-  }
-  for (int b = 1; b < d->nbody; b++) {
-    uint32_t anc = 0;
-    for (int bb = b; bb > 0; bb = d->body_parentid[bb]) anc |= 1u << bb;
-    f.body_ancmask[b] = anc;
-    const int p = d->body_parentid[b];
-    const bool bfree = d->body_jntnum[b] > 0 && d->jnt_type[d->body_jntadr[b]] == MJL_JNT_FREE;
-    if (p > 0) {
-      f.body_childmask[p] |= 1u << b;
-      if (!bfree) f.body_childmask_nf[p] |= 1u << b;
-    }
-    float mr = 0.f;  // the same float sum, in the same order, as a loop over the subtree would take
-    for (int c = b; c < d->body_subtree_end[b]; c++) mr += f.body_mass[c];
-    f.body_rootmass[b] = mr;
-  }
-  for (int j = 0; j < d->njnt; j++) {
-    const int b = d->jnt_bodyid[j];
-    f.body_jgather[d->jnt_type[j] == MJL_JNT_FREE ? b : d->body_parentid[b]] |= 1u << j;
-  }
-  int nlim = 0;
-  for (int j = 0; j < d->njnt; j++) {
-    if (d->jnt_type[j] != MJL_JNT_FREE && d->jnt_type[j] != MJL_JNT_HINGE) {
-      delete M; return fail(MJL_ERR_UNSUPPORTED, "joint type %d not supported", d->jnt_type[j]);
-    }
-    if (d->jnt_type[j] == MJL_JNT_FREE && d->body_jntadr[d->jnt_bodyid[j]] != j) {
-      delete M; return fail(MJL_ERR_UNSUPPORTED, "free joint must be the first joint of its body");
-    }
-    f.jnt_type[j] = d->jnt_type[j]; f.jnt_qposadr[j] = d->jnt_qposadr[j]; f.jnt_dofadr[j] = d->jnt_dofadr[j];
-    f.jnt_limited[j] = d->jnt_limited[j];
-    nlim += (d->jnt_limited[j] && d->jnt_type[j] == MJL_JNT_HINGE);
-    for (int i = 0; i < 3; i++) { f.jnt_pos[j][i] = (float)d->jnt_pos[j][i]; f.jnt_axis[j][i] = (float)d->jnt_axis[j][i]; }
-    f.jnt_range[j][0] = (float)d->jnt_range[j][0]; f.jnt_range[j][1] = (float)d->jnt_range[j][1];
-    f.jnt_stiffness[j] = (float)d->jnt_stiffness[j]; f.jnt_margin[j] = (float)d->jnt_margin[j];
-    f.jnt_solref[j][0] = (float)d->jnt_solref[j][0]; f.jnt_solref[j][1] = (float)d->jnt_solref[j][1];
-    for (int i = 0; i < 5; i++) f.jnt_solimp[j][i] = (float)d->jnt_solimp[j][i];
-  }
-  int anyd = 0;
-  for (int k = 0; k < d->nv; k++) {
-    f.dof_bodyid[k] = d->dof_bodyid[k]; f.dof_jntid[k] = d->dof_jntid[k]; f.dof_parentid[k] = d->dof_parentid[k];
-    f.dof_damping[k] = (float)d->dof_damping[k]; f.dof_armature[k] = (float)d->dof_armature[k];
-    f.dof_invweight0[k] = (float)d->dof_invweight0[k];
-    anyd |= d->dof_damping[k] > 0;
-  }
-  f.any_damping = anyd;
-  for (int i = 0; i < d->nq; i++) { f.qpos0[i] = (float)d->qpos0[i]; f.qpos_spring[i] = (float)d->qpos_spring[i]; }
-  for (int g = 0; g < d->ngeom; g++) {
-    f.geom_type[g] = d->geom_type[g]; f.geom_bodyid[g] = d->geom_bodyid[g];
-    double gm[9];
-    q2m_host(d->geom_quat[g], gm);
-    for (int i = 0; i < 3; i++) {
-      f.geom_pos[g][i] = (float)d->geom_pos[g][i];
-      f.geom_zaxis[g][i] = (float)gm[3 * i + 2];
-      f.geom_size[g][i] = (float)d->geom_size[g][i];
-    }
-  }
-  int ncon_max = 0, nefc_max = nlim;
-  for (int p = 0; p < d->npair; p++) {
-    int kind = d->pair_kind[p];
-    if (kind < MJL_COL_PLANE_SPHERE || kind > MJL_COL_CAPSULE_CAPSULE) {
-      delete M; return fail(MJL_ERR_UNSUPPORTED, "collision kind %d not supported", kind);
-    }
-    if (d->pair_condim[p] != 1 && d->pair_condim[p] != 3) {
-      delete M; return fail(MJL_ERR_UNSUPPORTED, "condim %d not supported", d->pair_condim[p]);
-    }
-    f.pair_geom1[p] = d->pair_geom1[p]; f.pair_geom2[p] = d->pair_geom2[p]; f.pair_kind[p] = kind;
-    f.pair_condim[p] = d->pair_condim[p];
-    f.pair_mu[p] = (float)d->pair_friction[p][0];
-    f.pair_solref[p][0] = (float)d->pair_solref[p][0]; f.pair_solref[p][1] = (float)d->pair_solref[p][1];
-    for (int i = 0; i < 5; i++) f.pair_solimp[p][i] = (float)d->pair_solimp[p][i];
-    f.pair_includemargin[p] = (float)(d->pair_margin[p] - d->pair_gap[p]);
-    int b1 = d->geom_bodyid[d->pair_geom1[p]], b2 = d->geom_bodyid[d->pair_geom2[p]];
-    double tran = d->body_invweight0[b1][0] + d->body_invweight0[b2][0];
-    if (d->pair_condim[p] == 1) f.pair_invweight[p] = (float)tran;
-    else {  // pyramidal: common invweight for every edge (constraint._efc_contact_pyramidal)
-      double mu = d->pair_friction[p][0];
-      double iw = tran + mu * mu * tran;
-      f.pair_invweight[p] = (float)(iw * 2 * mu * mu / d->impratio);
-    }
-    int nc = kind == MJL_COL_PLANE_CAPSULE ? 2 : 1;
-    ncon_max += nc;
-    nefc_max += nc * (d->pair_condim[p] == 1 ? 1 : 2 * (d->pair_condim[p] - 1));
-  }
-  for (int s = 0; s < d->nsite; s++) {
-    f.site_bodyid[s] = d->site_bodyid[s];
-    double sm[9];
-    q2m_host(d->site_quat[s], sm);
-    for (int i = 0; i < 9; i++) f.site_mat[s][i] = (float)sm[i];
-    for (int i = 0; i < 3; i++) { f.site_pos[s][i] = (float)d->site_pos[s][i]; f.site_size[s][i] = (float)d->site_size[s][i]; }
-  }
-  for (int u = 0; u < d->nu; u++) {
-    int j = d->actuator_trnid[u];
-    if (j < 0 || j >= d->njnt || d->jnt_type[j] != MJL_JNT_HINGE) {
-      delete M; return fail(MJL_ERR_UNSUPPORTED, "actuator %d: only hinge joint transmission supported", u);
-    }
-    f.actuator_dof[u] = d->jnt_dofadr[j];
-    f.actuator_ctrllimited[u] = d->actuator_ctrllimited[u];
-    f.actuator_gear[u] = (float)d->actuator_gear[u];
-    f.actuator_ctrlrange[u][0] = (float)d->actuator_ctrlrange[u][0];
-    f.actuator_ctrlrange[u][1] = (float)d->actuator_ctrlrange[u][1];
-  }
-  for (int t = 0; t < d->ntendon; t++) {
-    f.tendon_num[t] = d->tendon_num[t]; f.tendon_limited[t] = d->tendon_limited[t];
-    for (int w = 0; w < d->tendon_num[t]; w++) {
-      int j = d->tendon_jnt[t][w];
-      f.tendon_qadr[t][w] = d->jnt_qposadr[j];
-      f.tendon_dof[t][w] = d->jnt_dofadr[j];
-      f.tendon_coef[t][w] = (float)d->tendon_coef[t][w];
-    }
-    f.tendon_range[t][0] = (float)d->tendon_range[t][0]; f.tendon_range[t][1] = (float)d->tendon_range[t][1];
-    f.tendon_margin[t] = (float)d->tendon_margin[t];
-    f.tendon_solref[t][0] = (float)d->tendon_solref[t][0]; f.tendon_solref[t][1] = (float)d->tendon_solref[t][1];
-    for (int i = 0; i < 5; i++) f.tendon_solimp[t][i] = (float)d->tendon_solimp[t][i];
-    f.tendon_invweight0[t] = (float)d->tendon_invweight0[t];
-    nefc_max += d->tendon_limited[t];
-  }
-  for (int s = 0; s < d->nsensor; s++) {
-    if (d->sensor_type[s] != MJL_SENS_TOUCH) { delete M; return fail(MJL_ERR_UNSUPPORTED, "sensor type"); }
-    f.sensor_type[s] = d->sensor_type[s]; f.sensor_objid[s] = d->sensor_objid[s]; f.sensor_adr[s] = d->sensor_adr[s];
-  }
-  // packed per-lane records
-  for (int b = 0; b < d->nbody; b++) {
-    BodyRec& r = f.brec[b];
-    r.parent = d->body_parentid[b]; r.level = d->body_level[b];
-    r.jntadr = d->body_jntadr[b]; r.jntnum = d->body_jntnum[b];
-    r.dofadr = d->body_dofadr[b]; r.dofnum = d->body_dofnum[b];
-    r.subtree_end = d->body_subtree_end[b]; r.rootid = d->body_rootid[b];
-    r.isfree = d->body_jntnum[b] > 0 && d->jnt_type[d->body_jntadr[b]] == MJL_JNT_FREE;
-    r.qadr = r.isfree ? d->jnt_qposadr[d->body_jntadr[b]] : 0;
-    if (r.isfree && d->body_jntnum[b] != 1) {
-      delete M; return fail(MJL_ERR_UNSUPPORTED, "a body with a free joint must have no other joint");
-    }
-    for (int i = 0; i < 3; i++) { r.pos[i] = f.body_pos[b][i]; r.ipos[i] = f.body_ipos[b][i]; }
-    for (int i = 0; i < 4; i++) r.quat[i] = f.body_quat[b][i];
-    r.mass = f.body_mass[b];
-    for (int i = 0; i < 6; i++) r.inertia[i] = f.body_inertia[b][i];
-    for (int k = 0; k < 3 && k < d->body_jntnum[b]; k++) {
-      const int j = d->body_jntadr[b] + k;
-      for (int i = 0; i < 3; i++) { f.bhinge[b][k].pos[i] = f.jnt_pos[j][i]; f.bhinge[b][k].axis[i] = f.jnt_axis[j][i]; }
-    }
-  }
-  for (int g = 0; g < d->ngeom; g++) {
-    FrameRec& r = f.frec[g];
-    r.body = f.geom_bodyid[g];
-    for (int i = 0; i < 3; i++) { r.pos[i] = f.geom_pos[g][i]; r.mat[i] = f.geom_zaxis[g][i]; }
-  }
-  for (int st = 0; st < d->nsite; st++) {
-    FrameRec& r = f.frec[32 + st];
-    r.body = f.site_bodyid[st];
-    for (int i = 0; i < 3; i++) r.pos[i] = f.site_pos[st][i];
-    for (int i = 0; i < 9; i++) r.mat[i] = f.site_mat[st][i];
-  }
-  for (int j = 0; j < d->njnt; j++) {
-    JntRec& r = f.jrec[j];
-    for (int i = 0; i < 3; i++) { r.pos[i] = f.jnt_pos[j][i]; r.axis[i] = f.jnt_axis[j][i]; }
-    r.qadr = d->jnt_qposadr[j];
-    r.qpos0 = f.qpos0[r.qadr];
-    r.body = d->jnt_bodyid[j]; r.parent = d->body_parentid[r.body];
-    r.isfree = d->jnt_type[j] == MJL_JNT_FREE; r.dofadr = d->jnt_dofadr[j];
-  }
-  for (int k = 0; k < d->nv; k++) {
-    DofRec& r = f.drec[k];
-    int j = d->dof_jntid[k];
-    r.bodyid = d->dof_bodyid[k]; r.jntid = j; r.rootid = d->body_rootid[r.bodyid];
-    r.kfree = d->jnt_type[j] == MJL_JNT_FREE ? k - d->jnt_dofadr[j] : -1;
-    uint32_t am = 0;
-    for (int a = k; a >= 0; a = d->dof_parentid[a]) am |= 1u << a;
-    r.ancmask = am;
-    r.qadr_spring = d->jnt_type[j] == MJL_JNT_HINGE ? d->jnt_qposadr[j] : -1;
-    r.damping = f.dof_damping[k]; r.armature = f.dof_armature[k];
-    r.stiffness = f.jnt_stiffness[j];
-    r.qpos_spring = r.qadr_spring >= 0 ? f.qpos_spring[r.qadr_spring] : 0.f;
-    r.invweight0 = f.dof_invweight0[k];
-  }
-  for (int g = 0; g < d->ngeom; g++) f.body_geommask[d->geom_bodyid[g]] |= 1u << g;
-  for (int k = 0; k < d->nv; k++)  // descendants-or-self of each dof
-    for (int a = k; a >= 0; a = d->dof_parentid[a]) f.dof_descmask[a] |= 1u << k;
-  for (int p = 0; p < d->npair; p++) {
-    PairRec& r = f.prec[p];
-    r.g1 = f.pair_geom1[p]; r.g2 = f.pair_geom2[p]; r.kind = f.pair_kind[p]; r.condim = f.pair_condim[p];
-    r.r1 = f.geom_size[r.g1][0]; r.h1 = f.geom_size[r.g1][1];
-    r.r2 = f.geom_size[r.g2][0]; r.h2 = f.geom_size[r.g2][1];
-    r.includemargin = f.pair_includemargin[p]; r.mu = f.pair_mu[p]; r.invweight = f.pair_invweight[p];
-    r.b1 = d->geom_bodyid[r.g1]; r.b2 = d->geom_bodyid[r.g2];
-    r.mask1 = f.body_dofmask[r.b1]; r.mask2 = f.body_dofmask[r.b2];
-  }
-  for (int j = 0; j < d->njnt; j++) {
-    LimRec& r = f.jlim[j];
-    r.on = f.jnt_limited[j] && f.jnt_type[j] == MJL_JNT_HINGE;
-    r.qadr = f.jnt_qposadr[j]; r.dofadr = f.jnt_dofadr[j];
-    r.lo = f.jnt_range[j][0]; r.hi = f.jnt_range[j][1]; r.margin = f.jnt_margin[j];
-    r.invweight = f.dof_invweight0[r.dofadr];
-    for (int i = 0; i < 2; i++) r.solref[i] = f.jnt_solref[j][i];
-    for (int i = 0; i < 5; i++) r.solimp[i] = f.jnt_solimp[j][i];
-  }
-  for (int t = 0; t < d->ntendon; t++) {
-    LimRec& r = f.tlim[t];
-    r.on = f.tendon_limited[t];
-    r.lo = f.tendon_range[t][0]; r.hi = f.tendon_range[t][1]; r.margin = f.tendon_margin[t];
-    r.invweight = f.tendon_invweight0[t];
-    for (int i = 0; i < 2; i++) r.solref[i] = f.tendon_solref[t][i];
-    for (int i = 0; i < 5; i++) r.solimp[i] = f.tendon_solimp[t][i];
-  }
-  M->nefc_max = nefc_max;
-  M->ncon_max = ncon_max;
   // compact kernel instantiation when the model fits the humanoid capacities, generic otherwise
   M->nvc = (d->nv <= DHum::NV && d->nbody <= DHum::NB && d->njnt <= DHum::NJ && d->ngeom <= DHum::NG) ? 0 : 1;
-  *out = M;
+  *out = M.release();
   return MJL_OK;
 }
 

@@ -1,5 +1,5 @@
 // Device-side model constants (float32) and kernel parameter block.
-// Built on the host from mjlModelDesc (include/mjx355.h) by mjl_model_create; lives in device
+// Built on the host from mjlModelDesc (include/mjx355.h) by model_build (model_host.h); lives in device
 // global memory, read through the scalar/vector caches (a few KB, shared by every env).
 #pragma once
 #include <stdint.h>
@@ -60,16 +60,34 @@ struct alignas(16) LimRec {
   float solref[2], solimp[5], pad1;
 };
 
+// ModelF holds exactly what a kernel reads. Host staging does not belong here: a value the kernels take
+// only through a record is written into the record straight from mjlModelDesc (model_host.h) and has no
+// flat array. A member is added here together with the kernel read that needs it, and removed with it.
+//
+// Constants that still have two homes, and who reads which (moving a read from one home to the other
+// changes a kernel's loads: a change of its own, with a measurement):
+//   body_subtree_end   flat: subtree centres of mass over the roots (step kinematics), the renderer's
+//                      tracking camera; BodyRec.subtree_end: the subtree sums of CRB and RNE
+//   jnt_qposadr        flat: the limit rows' position cotangent (adjoint, by row id); JntRec.qadr /
+//                      BodyRec.qadr: kinematics, integration and their reverse passes, the renderer;
+//                      LimRec.qadr: the limit rows (step); DofRec.qadr_spring: passive forces
+//   jnt_range, jnt_solref, jnt_solimp, tendon_range, tendon_solref, tendon_solimp
+//                      flat: the adjoint of the constraint rows (by row id); LimRec (jlim / tlim): the
+//                      limit rows of the step
+//   dof_damping        flat: the integrator's damping term (step); DofRec.damping: passive forces and
+//                      their adjoint
+//   qpos0              flat: reset (whole vector); JntRec.qpos0: hinge angles in kinematics, its
+//                      reverse pass and the renderer
+//   qpos_spring        flat: whole vector, kept beside qpos0; DofRec.qpos_spring: passive forces
+//   geom_size          flat: the renderer's primitives; PairRec.r1/h1/r2/h2: collision and its adjoint
+//   site_bodyid        flat: touch sensors (by sensor_objid); FrameRec.body (lanes 32 + s): site frames
 struct ModelF {
   int nq, nv, nu, nbody, njnt, ngeom, nsite, ntendon, npair, nsensor, nsensordata;
-  int iterations, ls_iterations, solver, integrator, eulerdamp, maxlevel, nlimited, any_damping;
+  int iterations, ls_iterations, solver, integrator, eulerdamp, maxlevel, any_damping;
   int nroot, root[MJL_MAXBODY];  // kinematic roots: bodies whose parent is the world
-  float timestep, gravity[3], impratio, tolerance, ls_tolerance, meaninertia, scale;
+  float timestep, gravity[3], tolerance, ls_tolerance, scale;
 
-  int body_parentid[MJL_MAXBODY], body_rootid[MJL_MAXBODY], body_jntadr[MJL_MAXBODY];
-  int body_jntnum[MJL_MAXBODY], body_dofadr[MJL_MAXBODY], body_dofnum[MJL_MAXBODY];
-  int body_subtree_end[MJL_MAXBODY], body_level[MJL_MAXBODY];
-  uint32_t body_dofmask[MJL_MAXBODY];  // bit d set <=> dof d moves body b (ancestor chain)
+  int body_subtree_end[MJL_MAXBODY];
   // tree walks of the reverse passes as bit loops (no record loads in the loop): ancestors-or-self
   // (world excluded), children, children without a free joint, joints whose world anchor / axis
   // cotangents gather into b (b's free joint, hinges of b's children); the float sum of the masses
@@ -79,38 +97,30 @@ struct ModelF {
   uint32_t dof_descmask[MJL_MAXV];  // bit i set <=> dof i is this dof or one of its descendants
   uint32_t body_geommask[MJL_MAXBODY];  // bit g set <=> geom g belongs to body b
   float body_rootmass[MJL_MAXBODY];
-  float body_pos[MJL_MAXBODY][3], body_quat[MJL_MAXBODY][4], body_ipos[MJL_MAXBODY][3];
-  float body_inertia[MJL_MAXBODY][6], body_mass[MJL_MAXBODY], body_invweight0[MJL_MAXBODY][2];
 
-  int jnt_type[MJL_MAXJNT], jnt_qposadr[MJL_MAXJNT], jnt_dofadr[MJL_MAXJNT], jnt_limited[MJL_MAXJNT];
-  float jnt_pos[MJL_MAXJNT][3], jnt_axis[MJL_MAXJNT][3], jnt_range[MJL_MAXJNT][2];
-  float jnt_stiffness[MJL_MAXJNT], jnt_margin[MJL_MAXJNT], jnt_solref[MJL_MAXJNT][2];
-  float jnt_solimp[MJL_MAXJNT][5];
+  int jnt_qposadr[MJL_MAXJNT];
+  float jnt_range[MJL_MAXJNT][2], jnt_solref[MJL_MAXJNT][2], jnt_solimp[MJL_MAXJNT][5];
 
-  int dof_bodyid[MJL_MAXV], dof_jntid[MJL_MAXV], dof_parentid[MJL_MAXV];
-  float dof_damping[MJL_MAXV], dof_armature[MJL_MAXV], dof_invweight0[MJL_MAXV];
+  float dof_damping[MJL_MAXV];
   float qpos0[MJL_MAXQ], qpos_spring[MJL_MAXQ];
 
-  int geom_type[MJL_MAXGEOM], geom_bodyid[MJL_MAXGEOM];
-  float geom_pos[MJL_MAXGEOM][3], geom_zaxis[MJL_MAXGEOM][3], geom_size[MJL_MAXGEOM][3];
+  int geom_type[MJL_MAXGEOM];
+  float geom_size[MJL_MAXGEOM][3];
 
-  int pair_geom1[MJL_MAXPAIR], pair_geom2[MJL_MAXPAIR], pair_kind[MJL_MAXPAIR], pair_condim[MJL_MAXPAIR];
-  float pair_mu[MJL_MAXPAIR], pair_solref[MJL_MAXPAIR][2], pair_solimp[MJL_MAXPAIR][5];
-  float pair_includemargin[MJL_MAXPAIR], pair_invweight[MJL_MAXPAIR];  // invweight incl. pyramid factor
+  float pair_solref[MJL_MAXPAIR][2], pair_solimp[MJL_MAXPAIR][5];
 
   int site_bodyid[MJL_MAXSITE];
-  float site_pos[MJL_MAXSITE][3], site_mat[MJL_MAXSITE][9], site_size[MJL_MAXSITE][3];
+  float site_size[MJL_MAXSITE][3];
 
   int actuator_dof[MJL_MAXU], actuator_ctrllimited[MJL_MAXU];
   float actuator_gear[MJL_MAXU], actuator_ctrlrange[MJL_MAXU][2];
 
   int tendon_num[MJL_MAXTENDON], tendon_qadr[MJL_MAXTENDON][MJL_MAXTENWRAP];
-  int tendon_dof[MJL_MAXTENDON][MJL_MAXTENWRAP], tendon_limited[MJL_MAXTENDON];
+  int tendon_dof[MJL_MAXTENDON][MJL_MAXTENWRAP];
   float tendon_coef[MJL_MAXTENDON][MJL_MAXTENWRAP], tendon_range[MJL_MAXTENDON][2];
-  float tendon_margin[MJL_MAXTENDON], tendon_solref[MJL_MAXTENDON][2], tendon_solimp[MJL_MAXTENDON][5];
-  float tendon_invweight0[MJL_MAXTENDON];
+  float tendon_solref[MJL_MAXTENDON][2], tendon_solimp[MJL_MAXTENDON][5];
 
-  int sensor_type[MJL_MAXSENSOR], sensor_objid[MJL_MAXSENSOR], sensor_adr[MJL_MAXSENSOR];
+  int sensor_objid[MJL_MAXSENSOR], sensor_adr[MJL_MAXSENSOR];
 
   BodyRec brec[MJL_MAXBODY];
   JntRec jrec[MJL_MAXJNT];
