@@ -283,6 +283,39 @@ enum { MJL_RNG_JAX_PARTITIONABLE = 1, MJL_RNG_JAX_ORIGINAL = 2 };
  * (seed, counter): identical reset states to MJX for identical keys. */
 int mjl_env_set_reset_keys(mjlBatch* batch, const uint32_t* dev_keys, int mode);
 
+/* Applied forces (mjx.Data.qfrc_applied / xfrc_applied): caller-owned device buffers the batch reads at
+ * execution time (no copy, no allocation, capturable; update them in place). Both NULL detaches (default).
+ *   qfrc_applied  float [nenv, nv]        generalized force per dof, or NULL
+ *   xfrc_applied  float [nenv, nbody, 6]  per body (fx, fy, fz, tx, ty, tz) in the world frame, the force
+ *                                         acting at the body's inertial position xipos; row 0 (the world)
+ *                                         is ignored; or NULL
+ * While attached, mjl_forward, mjl_forward_contacts, mjl_step and mjl_env_step compute
+ *   qfrc_smooth = qfrc_passive - qfrc_bias + qfrc_actuator + qfrc_applied + sum_b J_b(xipos_b)' [f_b; t_b]
+ * (mj_xfrcAccumulate / support.xfrc_accumulate); the qfrc_bias / qfrc_passive / qfrc_actuator readouts keep
+ * their meaning. The buffers are inputs like ctrl: no kernel writes them (mjl_env_push aside) and a reset
+ * does not clear them. mjl_speedtest_step, mjl_env_reset, the auto-reset inside mjl_env_step and
+ * mjl_env_fill_reset_pool start from a fresh make_data and run with zero applied force.
+ * Not differentiated: every step VJP, record and replay entry (mjl_step_vjp*, mjl_env_step_vjp*,
+ * mjl_env_step_record*, mjl_env_step_vjp_replay*) returns MJL_ERR_UNSUPPORTED while anything is attached.
+ * A host-side pointer set; MJL_ERR_ARG for a null batch. */
+int mjl_batch_attach_applied(mjlBatch* batch, const float* qfrc_applied, const float* xfrc_applied);
+
+/* Random pushes: one launch per env step, before mjl_env_step (capturable). Writes row `body` of every
+ * env of the attached xfrc_applied (required, else MJL_ERR_ARG) and nothing else of it.
+ * timer int32 [nenv, 2], in/out: (steps_left of the running push, steps_to_next push). done [nenv] or NULL:
+ * the previous step's max(term, trunc). Uniforms u0, u1, u2 of env e: noise[e] (float [nenv, 3]) when given,
+ * else uniform01(seed, c ^ 2^62, e, i), i = 0..2, c = counter + the batch's counter base
+ * (mjl_batch_set_counter_base): a stream apart from the reset and pool draws. Per env, in this order:
+ *   done[e] > 0.5:    row = 0, steps_left = 0, steps_to_next = draw
+ *   steps_left > 0:   steps_left -= 1, row = 0 when it reaches 0
+ *   otherwise:        steps_to_next -= 1; at <= 0: row = (F cos th, F sin th, 0, 0, 0, 0), th = 2 pi u1,
+ *                     F = force_lo + u2 (force_hi - force_lo), steps_left = duration, steps_to_next = draw
+ * draw = interval_lo + min(floor(u0 (interval_hi - interval_lo + 1)), interval_hi - interval_lo).
+ * MJL_ERR_ARG: body outside 1..nbody-1, interval_lo < 1, interval_hi < interval_lo, duration < 1, null timer. */
+int mjl_env_push(mjlBatch* batch, int body, int32_t* timer, int interval_lo, int interval_hi, int duration,
+                 float force_lo, float force_hi, const float* done, uint64_t seed, uint64_t counter,
+                 const float* noise, void* stream);
+
 /* jax.random.split(key, num) for n keys at once: keys uint32 [n, 2] -> out [n, num, 2] (device). */
 int mjl_prng_split(const uint32_t* keys, int n, int num, int mode, uint32_t* out, void* stream);
 

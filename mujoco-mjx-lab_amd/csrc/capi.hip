@@ -104,6 +104,8 @@ struct mjlBatch {
   int pool_slots;
   StateBuf rs;
   float* rs_obs;
+  const float* qfrc_applied;  // caller-owned applied forces (mjl_batch_attach_applied), or null
+  const float* xfrc_applied;
 };
 
 extern "C" {
@@ -392,10 +394,28 @@ static bool one_wave_launch(const mjlBatch* B) {
   return on && B->nenv <= B->simds;
 }
 
-template <int MODE> static int launch(mjlBatch* B, const KParams& P, void* stream) {
+// APPLIED: the launch honours the batch's attached applied forces (forward, step and env step; every
+// other launch runs with zero applied force, whatever is attached). Nothing attached: the plain kernels.
+template <int MODE, bool APPLIED = false> static int launch(mjlBatch* B, const KParams& P0, void* stream) {
   HIPCHK(hipSetDevice(B->device));
   dim3 grid(B->nenv), block(64);
   constexpr bool kOneWave = MODE == MODE_ENV_STEP;
+  if constexpr (APPLIED) {
+    if (B->qfrc_applied || B->xfrc_applied) {
+      KParams P = P0;
+      P.qfrc_applied = B->qfrc_applied; P.xfrc_applied = B->xfrc_applied;
+      // (no one-wave instantiation: a second caller of the one-wave env_reset / global_rows_path changed the
+      // code the compiler makes for them and for the plain one-wave env step)
+      constexpr int kMode = MODE | MODE_APPLIED;
+      if (B->model->nvc == 0)
+        hipLaunchKernelGGL((step_kernel<DHum, kMode>), grid, block, 0, (hipStream_t)stream, P);
+      else
+        hipLaunchKernelGGL((step_kernel<DGen, kMode>), grid, block, 0, (hipStream_t)stream, P);
+      HIPCHK(hipGetLastError());
+      return MJL_OK;
+    }
+  }
+  const KParams& P = P0;
   if (B->model->nvc == 0 && kOneWave && one_wave_launch(B))
     hipLaunchKernelGGL((step_kernel<DHum, MODE, kOneWave ? 1 : MJL_MINWAVES>), grid, block, 0, (hipStream_t)stream, P);
   else if (B->model->nvc == 0)
@@ -412,7 +432,7 @@ int mjl_forward(mjlBatch* B, const float* mask, void* stream) {
   if (!B) return fail(MJL_ERR_ARG, "null batch");
   KParams P = make_params(B);
   P.mask = mask;
-  return launch<MODE_FORWARD>(B, P, stream);
+  return launch<MODE_FORWARD, true>(B, P, stream);
 }
 
 // Two launches: the forward pass with this call's rows in the global slab (the batch's
@@ -426,7 +446,7 @@ int mjl_forward_contacts(mjlBatch* B, const float* mask, int max_con, int32_t* n
   KParams P = make_params(B);
   P.mask = mask;
   P.force_global_rows = 1;
-  if (int rc = launch<MODE_FORWARD>(B, P, stream)) return rc;
+  if (int rc = launch<MODE_FORWARD, true>(B, P, stream)) return rc;
   ContactOut O;
   O.ncon = ncon; O.geom = geom; O.dim = dim; O.efc_adr = efc_adr;
   O.dist = dist; O.pos = pos; O.frame = frame; O.force = force; O.body_force = body_force;
@@ -448,7 +468,7 @@ int mjl_step(mjlBatch* B, const float* ctrl, void* stream) {
   if (!B) return fail(MJL_ERR_ARG, "null batch");
   KParams P = make_params(B);
   P.in_ctrl = ctrl;
-  return launch<MODE_STEP>(B, P, stream);
+  return launch<MODE_STEP, true>(B, P, stream);
 }
 
 int mjl_speedtest_step(mjlBatch* B, const float* vel, float* out, void* stream) {
@@ -504,7 +524,7 @@ int mjl_env_step(mjlBatch* B, const float* act, float* obs, float* rew, float* t
   P.auto_reset = auto_reset;
   set_seed_counter(P, seed, counter);
   if (B->d_pool_ctl && auto_reset) { P.rs = B->rs; P.rs_obs = B->rs_obs; P.pool_ctl = B->d_pool_ctl; }
-  return launch<MODE_ENV_STEP>(B, P, stream);
+  return launch<MODE_ENV_STEP, true>(B, P, stream);
 }
 
 int mjl_env_fill_reset_pool(mjlBatch* B, const int* dev_n, uint64_t seed, uint64_t counter, void* stream) {
@@ -533,6 +553,37 @@ int mjl_env_fill_reset_pool(mjlBatch* B, const int* dev_n, uint64_t seed, uint64
 int mjl_batch_set_counter_base(mjlBatch* B, const uint64_t* dev_counter_base) {
   if (!B) return fail(MJL_ERR_ARG, "null batch");
   B->ctr_base = (const unsigned long long*)dev_counter_base;
+  return MJL_OK;
+}
+
+int mjl_batch_attach_applied(mjlBatch* B, const float* qfrc_applied, const float* xfrc_applied) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  B->qfrc_applied = qfrc_applied;
+  B->xfrc_applied = xfrc_applied;
+  return MJL_OK;
+}
+
+int mjl_env_push(mjlBatch* B, int body, int32_t* timer, int interval_lo, int interval_hi, int duration,
+                 float force_lo, float force_hi, const float* done, uint64_t seed, uint64_t counter,
+                 const float* noise, void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (!B->xfrc_applied) return fail(MJL_ERR_ARG, "mjl_env_push needs an attached xfrc_applied");
+  if (!timer) return fail(MJL_ERR_ARG, "timer is required");
+  const int nbody = B->model->desc.nbody;
+  if (body < 1 || body >= nbody) return fail(MJL_ERR_ARG, "body %d outside 1..%d", body, nbody - 1);
+  if (interval_lo < 1 || interval_hi < interval_lo) return fail(MJL_ERR_ARG, "need 1 <= interval_lo <= interval_hi");
+  if (duration < 1) return fail(MJL_ERR_ARG, "duration must be >= 1");
+  HIPCHK(hipSetDevice(B->device));
+  PushArgs A;
+  A.xfrc = const_cast<float*>(B->xfrc_applied); A.timer = timer; A.done = done; A.noise = noise;
+  A.ctr_base = B->ctr_base;
+  A.nenv = B->nenv; A.nbody = nbody; A.body = body;
+  A.interval_lo = interval_lo; A.interval_hi = interval_hi; A.duration = duration;
+  A.force_lo = force_lo; A.force_hi = force_hi;
+  A.seed_lo = (uint32_t)seed; A.seed_hi = (uint32_t)(seed >> 32);
+  A.ctr_lo = (uint32_t)counter; A.ctr_hi = (uint32_t)(counter >> 32);
+  hipLaunchKernelGGL(env_push_kernel, dim3((unsigned)((B->nenv + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
+  HIPCHK(hipGetLastError());
   return MJL_OK;
 }
 
@@ -572,6 +623,14 @@ int mjl_env_reset(mjlBatch* B, const float* mask, uint64_t seed, uint64_t counte
 }  // extern "C"
 
 // ---------------------------------------------------------------- step VJP (APG backward)
+// The adjoint of J(q)' w with respect to q is not built: every VJP, record and replay entry checks this
+// before anything else, so a batch with applied forces attached is refused whatever the other arguments.
+static bool applied_attached(const mjlBatch* B) { return B && (B->qfrc_applied || B->xfrc_applied); }
+static int fail_applied() {
+  return fail(MJL_ERR_UNSUPPORTED, "step VJP / record / replay with applied forces attached: detach them "
+                                   "(mjl_batch_attach_applied(batch, NULL, NULL)) first");
+}
+
 template <bool ENV, int TM = 0> static int launch_vjp(mjlBatch* B, const VjpArgs& V0, void* stream,
                                                      const KParams* P0 = nullptr) {
   HIPCHK(hipSetDevice(B->device));
@@ -676,6 +735,7 @@ static VjpArgs record_io(mjlBatch* B, float* slot, const float* act, float* obs,
 
 // the env-step VJPs: the recompute (TM 0) or the replay of tape slot `slot` (TM 2)
 template <int TM> static int env_vjp(mjlBatch* B, int slot, VjpArgs V, void* stream) {
+  if (applied_attached(B)) return fail_applied();
   if (!B || !V.act || !V.g_qpos || !V.g_qvel || !V.g_rew || !V.g_aux || !V.o_qpos || !V.o_qvel || !V.o_ctrl || !V.o_aux)
     return fail(MJL_ERR_ARG, "bad argument");
   if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
@@ -706,6 +766,7 @@ int mjl_env_step_vjp_guarded(mjlBatch* B, const float* act, const float* g_qpos,
 
 int mjl_step_vjp_full(mjlBatch* B, const float* g_qpos, const float* g_qvel, const float* g_qacc_ws,
                       float* out_qpos, float* out_qvel, float* out_qacc_ws, float* out_ctrl, void* stream) {
+  if (applied_attached(B)) return fail_applied();
   if (!B || !g_qpos || !g_qvel || !out_qpos || !out_qvel || !out_ctrl) return fail(MJL_ERR_ARG, "bad argument");
   return launch_vjp<false>(B, vjp_io(nullptr, g_qpos, g_qvel, g_qacc_ws, nullptr, nullptr, out_qpos, out_qvel,
                                      out_qacc_ws, out_ctrl, nullptr, nullptr), stream);
@@ -721,6 +782,7 @@ int mjl_env_step_vjp_full(mjlBatch* B, const float* act, const float* g_qpos, co
 
 int mjl_env_step_record(mjlBatch* B, int slot, const float* act, float* obs, float* rew, float* term, float* trunc,
                         void* stream) {
+  if (applied_attached(B)) return fail_applied();
   if (!B || !act || !obs || !rew || !term || !trunc) return fail(MJL_ERR_ARG, "bad argument");
   if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
   float* const sp = tape_slot(B, slot);
@@ -732,6 +794,7 @@ int mjl_env_step_record(mjlBatch* B, int slot, const float* act, float* obs, flo
 int mjl_env_step_record_apg(mjlBatch* B, int slot, const float* act, float* obs, float* rew, float* term, float* trunc,
                             float gamma, float diverge_qvel, uint8_t* alive, float* disc, float* ret, float* dropped,
                             float* grew, float* rfin, void* stream) {
+  if (applied_attached(B)) return fail_applied();
   if (!B || !act || !obs || !rew || !term || !trunc || !alive || !disc || !ret || !dropped || !grew || !rfin)
     return fail(MJL_ERR_ARG, "bad argument");
   if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
@@ -1129,6 +1192,7 @@ extern "C" int mjl_env_step_record_apg_next(mjlBatch* B, int slot, const float* 
                                  float* dropped, float* grew, float* rfin, const float* mean, const float* var,
                                  int use_norm, float* o, float* on, uint8_t* alive_snap, int nl, const int* widths,
                                  const float* const* w_t, const float* const* b, float* const* ys, void* stream) {
+  if (applied_attached(B)) return fail_applied();
   if (!B || !act || !obs || !rew || !term || !trunc || !alive || !disc || !ret || !dropped || !grew || !rfin || !o ||
       !on || !alive_snap || (use_norm && (!mean || !var)))
     return fail(MJL_ERR_ARG, "bad argument");
@@ -1156,6 +1220,7 @@ extern "C" int mjl_env_step_vjp_replay_apg(mjlBatch* B, int slot, const float* a
                                            const int* widths, const float* const* w, float* const* ys, const float* o,
                                            const uint8_t* alive_snap, const float* mean, const float* var,
                                            int use_norm, void* stream) {
+  if (applied_attached(B)) return fail_applied();
   if (!B || !act || !g_qpos || !g_qvel || !g_rew || !g_aux || !out_qpos || !out_qvel || !out_act || !out_aux || !o ||
       !alive_snap || !w || !w[0] || (use_norm && (!mean || !var)))
     return fail(MJL_ERR_ARG, "bad argument");

@@ -131,7 +131,10 @@ struct ModelF {
   FrameRec frec[64];
 };
 
-enum Mode { MODE_FORWARD = 0, MODE_STEP = 1, MODE_SPEEDTEST = 2, MODE_ENV_STEP = 3, MODE_ENV_RESET = 4 };
+// MODE_APPLIED: a flag on MODE_FORWARD / MODE_STEP / MODE_ENV_STEP in step_kernel's template argument, the
+// instantiations that read the applied forces (KParams::qfrc_applied / xfrc_applied)
+enum Mode { MODE_FORWARD = 0, MODE_STEP = 1, MODE_SPEEDTEST = 2, MODE_ENV_STEP = 3, MODE_ENV_RESET = 4,
+            MODE_APPLIED = 8 };
 
 // per-env state rows, [nenv, dim] each
 struct StateBuf {
@@ -183,6 +186,9 @@ struct KParams {
   const int* pool_n;  // fill: slots to fill (device int, read at execution time)
   int pool_slot;    // fill: the slot this launch draws (-1: not a fill)
   int pool_slots;   // fill: pool capacity (slots per env)
+  // applied forces (mjl_batch_attach_applied), read by the MODE_APPLIED instantiations only
+  const float* qfrc_applied;  // [nenv, nv] or null
+  const float* xfrc_applied;  // [nenv, nbody, 6] world-frame (force, torque) at xipos, or null
 };
 
 }  // namespace mjl

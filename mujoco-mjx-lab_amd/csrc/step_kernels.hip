@@ -912,6 +912,52 @@ template <int NC, class Src, class Dst> INL void subtree_sums16(Src in, Dst out,
   }
 }
 
+// subtree_sums16 over two sets of 6-float rows in the same four MFMAs: output columns 0..5 are in0's
+// sums into out0 -- each output column is its own accumulate chain, so they are subtree_sums16<6>(in0,
+// out0) bit for bit -- and columns 6..11 in1's sums into out1 (the applied wrenches beside the body forces).
+template <class S0, class D0, class S1, class D1>
+INL void subtree_sums16_pair(S0 in0, D0 out0, S1 in1, D1 out1, int nbody, int end_lane, int lane) {
+  const int bi = (lane & 15) + 1, k = lane >> 4, j = lane & 15;
+  const int endb = __shfl(end_lane, bi);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < 4; t++) {
+    const int c = 1 + k + 4 * t;
+    const float a = (c >= bi && c < endb) ? 1.f : 0.f;
+    float bv = 0.f;
+    if (c < nbody && j < 6) bv = in0[c][j];
+    if (c < nbody && j >= 6 && j < 12) bv = in1[c][j - 6];
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const int b = 1 + 4 * k + r;
+    if (b < nbody && j < 6) out0[b][j] = acc[r];
+    if (b < nbody && j >= 6 && j < 12) out1[b][j - 6] = acc[r];
+  }
+}
+
+// Applied forces of one env, in this lane's registers (the MODE_APPLIED instantiations): body
+// `lane`'s xfrc_applied row (world frame: force, then torque, acting at xipos) and dof `lane`'s
+// qfrc_applied. A null buffer, the world body's row and the lanes past nbody / nv read as zero. Issued
+// beside the state loads, long before velocity_stage consumes them: clamped indices, no branch per load.
+struct AppliedRegs { float w[6], q; };
+INL AppliedRegs load_applied(const float* qfrc, const float* xfrc, int env, int nbody, int nv, int lane) {
+  AppliedRegs a;
+  const int ib = lane < nbody ? lane : 0, iv = lane < nv ? lane : 0;
+  const bool isb = lane > 0 && lane < nbody;
+#pragma unroll
+  for (int i = 0; i < 6; i++) a.w[i] = 0.f;
+  a.q = 0.f;
+  if (xfrc) {
+    const float* row = xfrc + ((size_t)env * nbody + ib) * 6;
+#pragma unroll
+    for (int i = 0; i < 6; i++) { const float x = row[i]; a.w[i] = isb ? x : 0.f; }
+  }
+  if (qfrc && nv > 0) { const float x = qfrc[(size_t)env * nv + iv]; a.q = lane < nv ? x : 0.f; }
+  return a;
+}
+
 // cinert (lane = body) and cdof (lane 32 + dof); crb (lane = body); M columns (lane = dof)
 template <class D> PHASE void com_pos_crb(MP m_, LDSA WS<D>* W, int lane, const KinPre& kp) {
   MP m = uniform_ptr(m_);
@@ -1018,7 +1064,13 @@ template <class D> PHASE void com_pos_crb(MP m_, LDSA WS<D>* W, int lane, const 
 // velocity stage: com_vel + rne forward pass by levels, backward by subtree ranges; passive
 // forces and actuation   [smooth.com_vel / smooth.rne / passive.passive / forward.fwd_actuation]
 // ---------------------------------------------------------------------------------------------
-template <class D> PHASE void velocity_stage(MP m_, LDSA WS<D>* W, int lane, const KinPre& kp) {
+// APPLIED (ap: this lane's applied forces): qfrc_smooth also gets qfrc_applied + sum_b J_b(xipos_b)' [f_b; t_b]
+// [mj_xfrcAccumulate / support.xfrc_accumulate]. Body b's wrench about its root's subtree com, [t + (xipos -
+// scom) x f; f], is what cdof projects: summed over subtrees beside the body forces (same MFMAs, columns
+// 6..11) and projected on cdof a second time, so frc_bias stays Data.qfrc_bias. Its rows live in crb (dead
+// since the mass matrix) and its subtree sums in cinert (dead once this stage's body forces are formed).
+template <class D, bool APPLIED = false>
+PHASE void velocity_stage(MP m_, LDSA WS<D>* W, int lane, const KinPre& kp, const AppliedRegs* ap = nullptr) {
   MP m = uniform_ptr(m_);
   const int maxlevel = m->maxlevel, nbody = m->nbody, nv = m->nv, nu = m->nu;
   const bool isb = lane > 0 && lane < nbody, isd = lane < nv, isu = lane < nu;
@@ -1091,8 +1143,27 @@ template <class D> PHASE void velocity_stage(MP m_, LDSA WS<D>* W, int lane, con
     for (int i = 0; i < 6; i++) f[i] = f1[i] + f2[i];
     for (int i = 0; i < 6; i++) W->cacc[lane][i] = f[i];
   }
+  if constexpr (APPLIED) {
+    if (isb) {
+      const int root = br.rootid;
+      const float r[3] = {W->xipos[lane][0] - W->scom[root][0], W->xipos[lane][1] - W->scom[root][1],
+                          W->xipos[lane][2] - W->scom[root][2]};
+      float rf[3];
+      cross3(rf, r, ap->w);
+      for (int i = 0; i < 3; i++) { W->crb[lane][i] = ap->w[3 + i] + rf[i]; W->crb[lane][3 + i] = ap->w[i]; }
+    }
+  }
   SYNC();
-  if (nbody <= 17) {  // subtree sums of cfrc into cvel (cvel is no longer needed)
+  if constexpr (APPLIED) {
+    if (nbody <= 17) {  // the same sums of cfrc into cvel, and the wrenches' into cinert
+      subtree_sums16_pair(W->cacc, W->cvel, W->crb, W->cinert, nbody, br.subtree_end, lane);
+    } else if (isb) {
+      float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, sw[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      for (int c = lane; c < br.subtree_end; c++)
+        for (int i = 0; i < 6; i++) { s[i] += W->cacc[c][i]; sw[i] += W->crb[c][i]; }
+      for (int i = 0; i < 6; i++) { W->cvel[lane][i] = s[i]; W->cinert[lane][i] = sw[i]; }
+    }
+  } else if (nbody <= 17) {  // subtree sums of cfrc into cvel (cvel is no longer needed)
     subtree_sums16<6>(W->cacc, W->cvel, nbody, br.subtree_end, lane);
   } else if (isb) {
     float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -1116,8 +1187,20 @@ template <class D> PHASE void velocity_stage(MP m_, LDSA WS<D>* W, int lane, con
     if (dr.qadr_spring >= 0) pf -= dr.stiffness * (W->qpos[dr.qadr_spring] - dr.qpos_spring);
     W->frc_passive[lane] = pf;
   }
+  float fapp = 0.f;  // APPLIED: this dof's applied generalized force
+  if constexpr (APPLIED) {
+    if (isd) {
+      LDSA float* c = W->cdof[lane];
+      LDSA float* fw = W->cinert[dr.bodyid];
+      fapp = ap->q + (c[0] * fw[0] + c[1] * fw[1] + c[2] * fw[2] + c[3] * fw[3] + c[4] * fw[4] + c[5] * fw[5]);
+    }
+  }
   SYNC();
-  if (isd) W->frc_smooth[lane] = W->frc_passive[lane] - W->frc_bias[lane] + W->frc_act[lane];
+  if (isd) {
+    float fs = W->frc_passive[lane] - W->frc_bias[lane] + W->frc_act[lane];
+    if constexpr (APPLIED) fs += fapp;
+    W->frc_smooth[lane] = fs;
+  }
   SYNC();
 }
 
@@ -2144,14 +2227,15 @@ NOINL void global_rows_path(MP m, LDSA WS<D>* W, float* scratch_env, int gmax_ef
 
 // the smooth dynamics: kinematics through qacc_smooth (no barrier after the last store: the caller's, or
 // build_rows', comes before its first read). STAMPS: forward()'s phase stamps of the timing build.
-template <class D, bool STAMPS> INL void smooth_forward(MP m, LDSA WS<D>* W, int lane, const KinPre& kp) {
+template <class D, bool STAMPS, bool APPLIED = false>
+INL void smooth_forward(MP m, LDSA WS<D>* W, int lane, const KinPre& kp, const AppliedRegs* ap = nullptr) {
   constexpr int LD = D::LD;
   if constexpr (STAMPS) STAMP(0, lane);
   kinematics<D>(m, W, lane, kp);
   if constexpr (STAMPS) STAMP(1, lane);
   com_pos_crb<D>(m, W, lane, kp);
   if constexpr (STAMPS) STAMP(2, lane);
-  velocity_stage<D>(m, W, lane, kp);
+  velocity_stage<D, APPLIED>(m, W, lane, kp, ap);
   if constexpr (STAMPS) STAMP(3, lane);
   // factor M into H: qacc_smooth now, CG preconditioner later
   float x = chol_factor_solve<D>(W->M, W->H, W->invd, m->nv, W->frc_smooth, lane);
@@ -2160,10 +2244,11 @@ template <class D, bool STAMPS> INL void smooth_forward(MP m, LDSA WS<D>* W, int
 }
 
 // full forward pass (mjx.forward)
-template <class D, int MW = MJL_MINWAVES> PHASE void forward(MP m_, LDSA WS<D>* W, float* scratch_env, int gmax_efc, int gmax_con,
-                                      int force_global, int lane, const KinPre& kp) {
+template <class D, int MW = MJL_MINWAVES, bool APPLIED = false>
+PHASE void forward(MP m_, LDSA WS<D>* W, float* scratch_env, int gmax_efc, int gmax_con, int force_global, int lane,
+                   const KinPre& kp, const AppliedRegs* ap = nullptr) {
   MP m = uniform_ptr(m_);
-  smooth_forward<D, true>(m, W, lane, kp);
+  smooth_forward<D, true, APPLIED>(m, W, lane, kp, ap);
   bool ok = false;
   if (!force_global) ok = build_rows<D, false>(m, W, lds_rows<D>(W), lane);
   STAMP(5, lane);
@@ -2635,7 +2720,18 @@ template <class D, bool AUX, class SB> INL void store_step_state(SB& S, LDSA WS<
 // instantiation does not take the whole 512-entry register file: it compiles to the same 248 VGPRs (+ 32
 // AGPRs) with fewer SGPR spills (69 against 94 in the env step); its gain is the compiler's schedule and
 // spill placement under the looser bound, not registers.
-template <class D, int MODE, int MW = MJL_MINWAVES> __global__ __launch_bounds__(64, MW) void step_kernel(KParams P) {
+//
+// MODE_ = a Mode, for forward, step and env step optionally | MODE_APPLIED: the launch then honours the
+// batch's attached applied forces (APPLIED below). They enter the step's own forward pass; the auto-reset's
+// forward (env_reset, the one shared out-of-line instantiation) starts from a fresh make_data and runs
+// without them. The flag rides in the mode so that the plain instantiations keep their names (the
+// profiler names in bench.py and tools/) and their body: moving the body into a function shared by two
+// kernels changed the register allocation of every existing instantiation.
+template <class D, int MODE_, int MW = MJL_MINWAVES> __global__ __launch_bounds__(64, MW) void step_kernel(KParams P) {
+  constexpr int MODE = MODE_ & ~MODE_APPLIED;
+  constexpr bool APPLIED = (MODE_ & MODE_APPLIED) != 0;
+  static_assert(!APPLIED || MODE == MODE_FORWARD || MODE == MODE_STEP || MODE == MODE_ENV_STEP,
+                "applied forces: forward, step and env step");
   __shared__ WS<D> Ws;
   __shared__ float aux_s[MJL_AUX_DIM + 3];
   LDSA WS<D>* W = (LDSA WS<D>*)&Ws;
@@ -2661,6 +2757,8 @@ template <class D, int MODE, int MW = MJL_MINWAVES> __global__ __launch_bounds__
     env_reset<D, MW>(m, W, kparams_late(), env, lane, aux, P.obs ? P.obs + (size_t)env * P.env->obs_dim : nullptr);
   } else {
     const KinPre kp = kin_prefetch(m, lane);  // issued before the state loads: the latencies overlap
+    AppliedRegs ap;
+    if constexpr (APPLIED) ap = load_applied(P.qfrc_applied, P.xfrc_applied, env, m->nbody, nv, lane);
     if (MODE == MODE_SPEEDTEST) {  // fresh make_data, qvel[0] = vel (mjx_humanoid_speed_test.py:50-55)
       if (lane < nq) W->qpos[lane] = m->qpos0[lane];
       if (lane < nv) W->qvel[lane] = (lane == 0) ? P.vel[env] : 0.f;
@@ -2671,7 +2769,10 @@ template <class D, int MODE, int MW = MJL_MINWAVES> __global__ __launch_bounds__
       load_step_state<D, MODE == MODE_ENV_STEP, true>(m, S, P.env, csrc, W, aux, env, lane);
     }
     SYNC();
-    forward<D, MW>(m, W, scratch_env, P.gmax_efc, P.gmax_con, P.force_global_rows, lane, kp);
+    if constexpr (APPLIED)
+      forward<D, MW, true>(m, W, scratch_env, P.gmax_efc, P.gmax_con, P.force_global_rows, lane, kp, &ap);
+    else
+      forward<D, MW>(m, W, scratch_env, P.gmax_efc, P.gmax_con, P.force_global_rows, lane, kp);
     if (MODE != MODE_FORWARD) integrate<D>(m, W, lane);
     STAMP(8, lane);
     const CSTA KParams& P = *kparams_late();  // the tail's arguments, loaded here (see kparams_late)
@@ -2729,6 +2830,52 @@ template <class D, int MODE, int MW = MJL_MINWAVES> __global__ __launch_bounds__
   if (MODE == MODE_ENV_RESET && P.pool_slot >= 0 && lane == 0) S.stats[(size_t)env * 4 + 3] = W->sc[SC_HEIGHT];
   }
   STAMP(39, lane);
+}
+
+// ---------------------------------------------------------------------------------------------
+// push generator (mjl_env_push): one thread per env writes row `body` of the env's xfrc_applied
+// ---------------------------------------------------------------------------------------------
+struct PushArgs {
+  float* xfrc;     // [nenv, nbody, 6]
+  int32_t* timer;  // [nenv, 2]: steps_left, steps_to_next
+  const float* done;   // [nenv] or null
+  const float* noise;  // [nenv, 3] or null
+  const unsigned long long* ctr_base;
+  int nenv, nbody, body, interval_lo, interval_hi, duration;
+  float force_lo, force_hi;
+  uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;
+};
+__global__ void env_push_kernel(PushArgs A) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= A.nenv) return;
+  float u[3];
+  if (A.noise) {
+    for (int i = 0; i < 3; i++) u[i] = A.noise[(size_t)e * 3 + i];
+  } else {  // a stream of its own: the counter's bit 62 keeps pushes off the reset and pool draws
+    const unsigned long long c =
+        (((unsigned long long)A.ctr_hi << 32 | A.ctr_lo) + (A.ctr_base ? *A.ctr_base : 0ull)) ^ (1ull << 62);
+    for (int i = 0; i < 3; i++) u[i] = uniform01(A.seed_lo, A.seed_hi, (uint32_t)c, (uint32_t)(c >> 32), e, i);
+  }
+  const int span = A.interval_hi - A.interval_lo;
+  const int next = A.interval_lo + min((int)floorf(u[0] * (float)(span + 1)), span);
+  float* row = A.xfrc + ((size_t)e * A.nbody + A.body) * 6;
+  int left = A.timer[2 * e], to_next = A.timer[2 * e + 1];
+  bool zero = false, push = false;
+  if (A.done && A.done[e] > 0.5f) {
+    zero = true; left = 0; to_next = next;
+  } else if (left > 0) {
+    zero = --left == 0;
+  } else if (--to_next <= 0) {
+    push = true; left = A.duration; to_next = next;
+  }
+  if (zero) {
+    for (int i = 0; i < 6; i++) row[i] = 0.f;
+  } else if (push) {  // horizontal, uniform in direction and magnitude; the angle's sine and cosine rounded once
+    const float th = 6.2831853071795864769f * u[1], F = A.force_lo + u[2] * (A.force_hi - A.force_lo);
+    row[0] = F * (float)cos((double)th); row[1] = F * (float)sin((double)th);
+    for (int i = 2; i < 6; i++) row[i] = 0.f;
+  }
+  A.timer[2 * e] = left; A.timer[2 * e + 1] = to_next;
 }
 
 }  // namespace mjl

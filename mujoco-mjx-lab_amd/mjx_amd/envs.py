@@ -74,6 +74,34 @@ class HumanoidEnv:
         check(lib().mjl_env_set_reset_keys(self.data.handle, None if keys is None else C.c_void_p(keys.data_ptr()),
                                            int(mode)))
 
+    def attach_applied(self, qfrc_applied: Optional[torch.Tensor] = None,
+                       xfrc_applied: Optional[torch.Tensor] = None):
+        """Applied forces for step() (Data.attach_applied): read at execution time, never written by a step
+        or cleared by a reset; resets and pooled resets run without them. Both None detaches."""
+        self.data.attach_applied(qfrc_applied, xfrc_applied)
+        self.xfrc_applied = xfrc_applied
+        if xfrc_applied is not None and getattr(self, "push_timer", None) is None:  # push()'s per-env timers
+            self.push_timer = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self.obs.device)
+
+    def push(self, body: int, interval: Tuple[int, int], duration: int, force: Tuple[float, float],
+             done: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+             counter: Optional[int] = None):
+        """One step of the random-push schedule, called before step() (mjl_env_push): every `interval`
+        (lo, hi) steps, drawn per env, a horizontal force of magnitude in `force` (lo, hi) and uniform
+        direction is held on `body` for `duration` steps in the attached xfrc_applied. `done` [num_envs]
+        (the previous step's max(term, trunc)) ends an env's push and redraws its interval. The timer tensor
+        is the env's. `noise` [num_envs, 3] replaces the on-device draws (tests); `counter` as in step()
+        (default: the counter the next step() will use; the push stream is a domain of its own)."""
+        if getattr(self, "xfrc_applied", None) is None:
+            raise MjlError("push needs attach_applied(xfrc_applied=...) first")
+        for t, n, what in ((done, self.num_envs, "done"), (noise, self.num_envs * 3, "noise")):
+            if t is not None and t.numel() != n:
+                raise MjlError(f"{what} must have {n} elements")
+        check(lib().mjl_env_push(self.data.handle, int(body), C.c_void_p(self.push_timer.data_ptr()),
+                                 int(interval[0]), int(interval[1]), int(duration), float(force[0]), float(force[1]),
+                                 _ptr(done), self.seed, self.counter + 1 if counter is None else int(counter),
+                                 _ptr(noise), _stream()))
+
     def _next_counter(self) -> int:
         self.counter += 1
         return self.counter

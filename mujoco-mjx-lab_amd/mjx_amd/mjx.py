@@ -117,6 +117,27 @@ class Data:
         mk = None if mask is None else mask.to(device=self.device, dtype=torch.float32).contiguous()
         check(lib().mjl_set(self._h, abi.FIELD[field], _ptr(v), _ptr(mk), _stream()))
 
+    def attach_applied(self, qfrc_applied: Optional[torch.Tensor] = None,
+                       xfrc_applied: Optional[torch.Tensor] = None):
+        """mjx.Data.qfrc_applied [nenv, nv] / xfrc_applied [nenv, nbody, 6] (world-frame force and torque at
+        xipos; row 0 ignored): forward, forward_contacts, step and the env step read the tensors at
+        execution time, so update them in place (`d.replace(xfrc_applied=x)` becomes `buf.copy_(x)`). Either
+        may be None; both None detaches. The step VJPs raise while anything is attached."""
+        for t, shape, what in ((qfrc_applied, (self.nenv, self.model.nv), "qfrc_applied"),
+                               (xfrc_applied, (self.nenv, self.model.nbody, 6), "xfrc_applied")):
+            if t is None:
+                continue
+            if tuple(t.shape) != shape:
+                raise MjlError(f"{what} must have shape {shape}")
+            if t.device != self.device:
+                raise MjlError(f"{what} must live on {self.device}")
+            _ptr(t)  # contiguous float32 CUDA
+        check(lib().mjl_batch_attach_applied(self._h, _ptr(qfrc_applied), _ptr(xfrc_applied)))
+        self._applied = (qfrc_applied, xfrc_applied)  # keep the buffers alive while the library points at them
+
+    def detach_applied(self):
+        self.attach_applied(None, None)
+
     def __getattr__(self, name):
         if name in _FIELD_DIM:
             return self.get(name)

@@ -1213,7 +1213,7 @@ class PPOTrainer:
 
     def __init__(self, cfg, env, eval_env=None, device="cuda", dist=None, out_dir: Optional[str] = None,
                  use_graph: bool = True, jax_keys: bool = False, fused_policy: bool = True,
-                 reset_pool: int = 16, update_graph: bool = True):
+                 reset_pool: int = 16, update_graph: bool = True, push: Optional[dict] = None):
         """jax_keys: draw every env reset (initial, auto-reset, eval) from the jax.random key chain
         train_ppo.py derives from cfg.seed (:88-118, :132/:150-151 per rollout step, :325, :359,
         :419, eval :268-293), so the reset stream equals the reference's for the same seed.
@@ -1224,7 +1224,10 @@ class PPOTrainer:
         merged by the env steps, instead of each finishing env resetting at the end of its step;
         0 = in place only. Not with jax_keys (those resets are drawn per step).
         update_graph: the update's minibatch steps replay hipGraphs (PPOUpdater) from the second
-        iteration on."""
+        iteration on.
+        push: random pushes on the training envs (HumanoidEnv.push's body / interval / duration / force),
+        one launch before each rollout step, inside the captured rollout; None (default): nothing is
+        attached and the rollout is launch for launch what it was. Evaluation envs are never pushed."""
         self.cfg, self.env, self.eval_env, self.dist = cfg, env, eval_env, dist
         self.rank = dist.get_rank() if dist is not None else 0
         self.world = dist.get_world_size() if dist is not None else 1
@@ -1256,6 +1259,15 @@ class PPOTrainer:
         if reset_pool > 0 and not self.jax_keys and self.device.type == "cuda" and hasattr(env, "enable_reset_pool"):
             env.enable_reset_pool(int(reset_pool))
             self._pool_n = torch.full((1,), min(4, int(reset_pool)), dtype=torch.int32, device=self.device)
+        self.push = None
+        if push:
+            if not hasattr(env, "push"):
+                raise ValueError("push needs an env with applied forces (HumanoidEnv)")
+            self.push = dict(push)
+            self.push_xfrc = torch.zeros((env.num_envs, env.sys.nbody, 6), device=self.device)
+            env.attach_applied(xfrc_applied=self.push_xfrc)
+            # the previous step's max(term, trunc); all ones first, so the first call draws every env's interval
+            self._push_done = torch.ones(env.num_envs, device=self.device)
         self.allreduce_events = None  # a list to time the per-minibatch all-reduce (bench.py, event_ms)
         self.phase_events = None  # a list: per iteration 4 CUDA events (rollout | between | update), bench.py
         self.total_env_steps = 0.0
@@ -1337,6 +1349,8 @@ class PPOTrainer:
                 gaussian_logprob(mean, log_std, act, out=bf["logp"][t])
             # physics + reward + obs + merge_if_done, one launch
             out = (bf["obs"][t + 1], bf["rew"][t], bf["term"][t], bf["trunc"][t])
+            if self.push is not None:
+                env.push(done=self._push_done, counter=t + 1 if graph else None, **self.push)
             if graph:
                 env.step(act, out=out, counter=t + 1)
             elif hasattr(env, "ctr_base"):
@@ -1344,6 +1358,8 @@ class PPOTrainer:
             else:  # envs without output buffers (CPU stand-ins)
                 for dst, src in zip(out, env.step(act)):
                     dst.copy_(src)
+            if self.push is not None:
+                torch.maximum(out[2], out[3], out=self._push_done)
 
     @torch.no_grad()
     def collect_rollout(self):

@@ -22,7 +22,7 @@ from mjx_amd.envs import HumanoidEnv, resolve_ids  # noqa: E402
 from mjx_amd.ppo import PPOTrainer  # noqa: E402
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default=None, help="reference-style config.json (env / ppo sections)")
     ap.add_argument("--test", action="store_true", help="tiny run (reference config_test.json spirit)")
@@ -35,8 +35,31 @@ def main():
                     help="draw env resets from train_ppo.py's jax.random key chain (same reset stream as the reference)")
     ap.add_argument("--save-video", action="store_true",
                     help="per eval, write the policy rollout's qpos history (.npz) and its rendered video (.gif)")
-    a = ap.parse_args()
+    ap.add_argument("--push-force", type=float, nargs=2, metavar=("LO", "HI"), default=None,
+                    help="random horizontal pushes on the training envs: force magnitude range in N (off by default)")
+    ap.add_argument("--push-interval", type=int, nargs=2, metavar=("LO", "HI"), default=None,
+                    help="env steps between pushes, drawn per env (default 100 200)")
+    ap.add_argument("--push-duration", type=int, default=None, metavar="K", help="env steps a push lasts (default 5)")
+    ap.add_argument("--push-body", default=None, metavar="NAME", help="pushed body (default: the env's pelvis body)")
+    a = ap.parse_args(argv)
+    if a.push_force is None and (a.push_interval or a.push_duration is not None or a.push_body):
+        ap.error("--push-interval / --push-duration / --push-body need --push-force LO HI")
+    return a
 
+
+def push_config(a, model, env_cfg):
+    """PPOTrainer's `push` from the --push-* flags: None without --push-force (no attach, no new launches)."""
+    if a.push_force is None:
+        return None
+    body = env_cfg.pelvis_body_id if a.push_body is None else model.name2id("body", a.push_body)
+    if body < 1:
+        raise SystemExit(f"--push-body: no body named {a.push_body!r}")
+    return {"body": body, "interval": tuple(a.push_interval or (100, 200)),
+            "duration": 5 if a.push_duration is None else a.push_duration, "force": tuple(a.push_force)}
+
+
+def main():
+    a = parse_args()
     cfg = PPOConfig.from_json(a.config) if a.config else reference_ppo_config()
     if a.test:
         cfg.num_envs, cfg.rollout_length, cfg.minibatch_size, cfg.total_iterations = 64, 16, 256, 3
@@ -67,7 +90,8 @@ def main():
     out = None
     if rank == 0:
         out = os.path.join(cfg.results_dir, time.strftime("%Y%m%d_%H%M%S") + "_ppo")
-    tr = PPOTrainer(cfg, env, eval_env, device=f"cuda:{local}", dist=dist, out_dir=out, jax_keys=a.jax_keys)
+    tr = PPOTrainer(cfg, env, eval_env, device=f"cuda:{local}", dist=dist, out_dir=out, jax_keys=a.jax_keys,
+                    push=push_config(a, model, env_cfg))
     tr.train()
     if dist is not None:
         dist.destroy_process_group()

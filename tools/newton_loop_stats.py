@@ -155,7 +155,7 @@ def main():
     pats = sys.argv[2:] or ["step_kernel", "apg", "vjp"]
     ks = kernels(path)
     for name, body in ks.items():
-        m = re.search(r"step_kernelINS_4DimsI.*?EEELi(\d)ELi\d+EEE", name)
+        m = re.search(r"step_kernelINS_4DimsI.*?EEELi(\d+)ELi\d+EEE", name)
         if not m or m.group(1) not in ("2", "3"):  # MODE_SPEEDTEST = 2, MODE_ENV_STEP = 3
             continue
         bl, succ = blocks(body)
