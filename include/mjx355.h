@@ -183,10 +183,48 @@ int mjl_batch_nenv(const mjlBatch* batch);
  * mjl_env_step_vjp_replay), each holding one env step's forward workspace for every env
  * (~50 KB per env and slot for the humanoid; call outside stream capture; 0 frees it).
  * MJL_OPT_RESET_POOL (default 0): value = slots per env (<= 64) of the reset pool that
- * mjl_env_fill_reset_pool fills (call outside stream capture; 0 frees it). */
+ * mjl_env_fill_reset_pool fills (call outside stream capture; 0 frees it).
+ * MJL_OPT_PER_ENV_MODEL (default 0): 1 gives every env a model block of its own, filled with the
+ * model's values (nenv x 45936 bytes, the size of one device model block: 94 MB for 2048 envs; call
+ * outside stream capture; 0 frees them). See mjl_batch_set_model_params. */
 enum { MJL_OPT_STORE_DERIVED = 0, MJL_OPT_FORCE_GLOBAL_ROWS = 1, MJL_OPT_VJP_UNROLLED = 2, MJL_OPT_RESET_POOL = 3,
-       MJL_OPT_VJP_TAPE = 4 };
+       MJL_OPT_VJP_TAPE = 4, MJL_OPT_PER_ENV_MODEL = 5 };
 int mjl_batch_set_option(mjlBatch* batch, int option, int value);
+
+/* Per-env model parameters (domain randomisation; in MJX jax.vmap(step, in_axes=(model_axes, 0)) over a
+ * model whose fields carry a batch axis, Brax's domain_randomize). The fields that can differ per env, each
+ * float32 device rows [nenv, dim]:
+ *   MJL_MP_BODY_MASS      body_mass                            dim nbody
+ *   MJL_MP_BODY_INERTIA   body_inertia (xx yy zz xy xz yz)     dim nbody * 6
+ *   MJL_MP_DOF_DAMPING    dof_damping                          dim nv
+ *   MJL_MP_DOF_ARMATURE   dof_armature                         dim nv
+ *   MJL_MP_ACTUATOR_GEAR  actuator_gear                        dim nu
+ *   MJL_MP_PAIR_FRICTION  pair_friction[p][0], the mu of the pyramidal rows   dim npair
+ *                         (the sliding coefficient of both tangent directions: MuJoCo's [0] and [1], always equal)
+ * mjl_model_param_dim returns the dim (-1: null model or unknown id).
+ * Semantics: env e runs the model whose descriptor has these fields replaced by env e's values (each taken
+ * as (double)(float)) and nothing else recomputed, as sys.tree_replace under vmap, which does not re-run
+ * mj_setConst: body_invweight0, dof_invweight0, tendon_invweight0 and meaninertia stay the model's; what is
+ * computed from the replaced fields follows them (the subtree masses, the damping flag, the contact rows'
+ * invweight (tran + mu^2 tran) 2 mu^2 / impratio). Env e's block is byte for byte the block mjl_model_create
+ * makes of that descriptor.
+ * mjl_batch_set_model_params: one launch, no allocation, no synchronisation, capturable; values[k] (k =
+ * MJL_MP_*, a table of MJL_NMP device pointers read by the host at the call) NULL keeps every env's current
+ * value of field k; envs with mask <= 0.5 keep their block (mask NULL = all); the values are read at
+ * execution time. MJL_ERR_ARG for a null batch / values or when MJL_OPT_PER_ENV_MODEL is off.
+ * mjl_batch_get_model_params copies field `param` of every env's block to dst [nenv, dim]: what the kernels
+ * will use.
+ * While the option is on, mjl_forward, mjl_forward_contacts, mjl_step, mjl_env_step (its in-kernel
+ * auto-reset and pooled resets included), mjl_env_reset and mjl_env_fill_reset_pool run env e on its block;
+ * pooled resets are computed with the blocks as they are at the fill. mjl_speedtest_step runs the model's
+ * own values. Not differentiated: every step VJP, record and replay entry returns MJL_ERR_UNSUPPORTED
+ * while the option is on. The renderer is not concerned (no geometric field). */
+#define MJL_NMP 6
+enum { MJL_MP_BODY_MASS = 0, MJL_MP_BODY_INERTIA = 1, MJL_MP_DOF_DAMPING = 2, MJL_MP_DOF_ARMATURE = 3,
+       MJL_MP_ACTUATOR_GEAR = 4, MJL_MP_PAIR_FRICTION = 5 };
+int mjl_model_param_dim(const mjlModel* model, int param);
+int mjl_batch_set_model_params(mjlBatch* batch, const float* const* values, const float* mask, void* stream);
+int mjl_batch_get_model_params(mjlBatch* batch, int param, float* dst, void* stream);
 
 /* Copy a per-env field to / from a device buffer [nenv, dim] (async on stream). `mask` (device,
  * float [nenv], may be NULL) restricts mjl_set to envs with mask > 0.5. */

@@ -106,7 +106,20 @@ struct mjlBatch {
   float* rs_obs;
   const float* qfrc_applied;  // caller-owned applied forces (mjl_batch_attach_applied), or null
   const float* xfrc_applied;
+  ModelF* d_model_env;      // MJL_OPT_PER_ENV_MODEL: one model block per env, or null
+  ParamStage* d_param_stage;  // what model_params_kernel needs beside the blocks (allocated with them)
 };
+
+// one launch of the per-env block builder: `fill` copies the shared block into every env's
+static int launch_model_params(mjlBatch* B, const float* const* values, const float* mask, int fill, void* stream) {
+  ModelParamArgs A;
+  A.nominal = B->d_model; A.blocks = B->d_model_env; A.stage = B->d_param_stage;
+  for (int k = 0; k < MJL_NMP; k++) A.v[k] = values ? values[k] : nullptr;
+  A.mask = mask; A.nenv = B->nenv; A.fill = fill;
+  hipLaunchKernelGGL(model_params_kernel, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
+}
 
 extern "C" {
 
@@ -212,6 +225,7 @@ void mjl_batch_destroy(mjlBatch* B) {
   (void)hipFree(B->d_unr);
   (void)hipFree(B->d_exp_stage);
   (void)hipFree(B->d_rs); (void)hipFree(B->d_pool_ctl); (void)hipFree(B->d_vtape);
+  (void)hipFree(B->d_model_env); (void)hipFree(B->d_param_stage);
   delete B;
 }
 
@@ -268,7 +282,53 @@ int mjl_batch_set_option(mjlBatch* B, int option, int value) {
     B->pool_slots = value;
     return MJL_OK;
   }
+  if (option == MJL_OPT_PER_ENV_MODEL) {
+    HIPCHK(hipSetDevice(B->device));
+    (void)hipFree(B->d_model_env); (void)hipFree(B->d_param_stage);
+    B->d_model_env = nullptr; B->d_param_stage = nullptr;
+    if (!value) return MJL_OK;
+    const size_t bytes = (size_t)B->nenv * sizeof(ModelF);
+    ParamStage st;
+    model_param_stage(&B->model->desc, st);
+    hipError_t e = hipMalloc(&B->d_model_env, bytes);
+    if (e == hipSuccess) e = hipMalloc(&B->d_param_stage, sizeof(ParamStage));
+    if (e == hipSuccess) e = hipMemcpy(B->d_param_stage, &st, sizeof(ParamStage), hipMemcpyHostToDevice);
+    int rc = MJL_OK;
+    if (e == hipSuccess) {
+      rc = launch_model_params(B, nullptr, nullptr, 1, nullptr);
+      if (rc == MJL_OK) e = hipStreamSynchronize(nullptr);
+    }
+    if (e != hipSuccess || rc != MJL_OK) {
+      (void)hipFree(B->d_model_env); (void)hipFree(B->d_param_stage);
+      B->d_model_env = nullptr; B->d_param_stage = nullptr;
+      return e != hipSuccess ? fail(MJL_ERR_HIP, "per-env model blocks (%zu bytes): %s", bytes, hipGetErrorString(e)) : rc;
+    }
+    return MJL_OK;
+  }
   return fail(MJL_ERR_ARG, "unknown option %d", option);
+}
+
+int mjl_model_param_dim(const mjlModel* m, int param) { return m ? model_param_dim(&m->desc, param) : -1; }
+
+int mjl_batch_set_model_params(mjlBatch* B, const float* const* values, const float* mask, void* stream) {
+  if (!B || !values) return fail(MJL_ERR_ARG, "null argument");
+  if (!B->d_model_env) return fail(MJL_ERR_ARG, "MJL_OPT_PER_ENV_MODEL not set");
+  HIPCHK(hipSetDevice(B->device));
+  return launch_model_params(B, values, mask, 0, stream);
+}
+
+int mjl_batch_get_model_params(mjlBatch* B, int param, float* dst, void* stream) {
+  if (!B || !dst) return fail(MJL_ERR_ARG, "null argument");
+  if (!B->d_model_env) return fail(MJL_ERR_ARG, "MJL_OPT_PER_ENV_MODEL not set");
+  const int dim = model_param_dim(&B->model->desc, param);
+  if (dim < 0) return fail(MJL_ERR_ARG, "unknown model parameter %d", param);
+  if (dim == 0) return MJL_OK;
+  HIPCHK(hipSetDevice(B->device));
+  const long n = (long)B->nenv * dim;
+  hipLaunchKernelGGL(model_params_get_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const ModelF*)B->d_model_env, param, B->nenv, dim, dst);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
 }
 
 }  // extern "C"
@@ -396,10 +456,28 @@ static bool one_wave_launch(const mjlBatch* B) {
 
 // APPLIED: the launch honours the batch's attached applied forces (forward, step and env step; every
 // other launch runs with zero applied force, whatever is attached). Nothing attached: the plain kernels.
+// With MJL_OPT_PER_ENV_MODEL on, every launch but the speed test's takes the per-env instantiation: forward,
+// step and env step the applied one too (null buffers when nothing is attached: the plain computation), so
+// that pushes and randomisation combine without a third set of kernels; the reset the plain one. (No one-wave
+// variant, as for the applied kernels.)
 template <int MODE, bool APPLIED = false> static int launch(mjlBatch* B, const KParams& P0, void* stream) {
   HIPCHK(hipSetDevice(B->device));
   dim3 grid(B->nenv), block(64);
   constexpr bool kOneWave = MODE == MODE_ENV_STEP;
+  if constexpr (MODE != MODE_SPEEDTEST) {
+    if (B->d_model_env) {
+      KParams P = P0;
+      P.m_env = B->d_model_env;
+      if constexpr (APPLIED) { P.qfrc_applied = B->qfrc_applied; P.xfrc_applied = B->xfrc_applied; }
+      constexpr int kMode = MODE | MODE_PER_ENV | (APPLIED ? MODE_APPLIED : 0);
+      if (B->model->nvc == 0)
+        hipLaunchKernelGGL((step_kernel<DHum, kMode>), grid, block, 0, (hipStream_t)stream, P);
+      else
+        hipLaunchKernelGGL((step_kernel<DGen, kMode>), grid, block, 0, (hipStream_t)stream, P);
+      HIPCHK(hipGetLastError());
+      return MJL_OK;
+    }
+  }
   if constexpr (APPLIED) {
     if (B->qfrc_applied || B->xfrc_applied) {
       KParams P = P0;
@@ -452,6 +530,9 @@ int mjl_forward_contacts(mjlBatch* B, const float* mask, int max_con, int32_t* n
   O.dist = dist; O.pos = pos; O.frame = frame; O.force = force; O.body_force = body_force;
   O.max_con = max_con;
   dim3 grid(B->nenv), block(64);
+  // The shared block also with MJL_OPT_PER_ENV_MODEL on: of the model, contacts_kernel reads prec[].g1 / g2 /
+  // includemargin and nbody, none of them a per-env field, and takes mu from the contact record the (per-env)
+  // forward pass wrote. A read of a MJL_MP_* field added there needs the env's block (d_model_env + env).
   if (B->model->nvc == 0)
     hipLaunchKernelGGL(contacts_kernel<DHum>, grid, block, 0, (hipStream_t)stream, (const ModelF*)B->d_model,
                        (const float*)B->s.stats, mask, B->d_scratch, B->scratch_stride, B->gmax_efc, B->gmax_con,
@@ -625,10 +706,12 @@ int mjl_env_reset(mjlBatch* B, const float* mask, uint64_t seed, uint64_t counte
 // ---------------------------------------------------------------- step VJP (APG backward)
 // The adjoint of J(q)' w with respect to q is not built: every VJP, record and replay entry checks this
 // before anything else, so a batch with applied forces attached is refused whatever the other arguments.
-static bool applied_attached(const mjlBatch* B) { return B && (B->qfrc_applied || B->xfrc_applied); }
+// Nor are the adjoints through per-env model blocks: the same entries refuse a batch with MJL_OPT_PER_ENV_MODEL on.
+static bool applied_attached(const mjlBatch* B) { return B && (B->qfrc_applied || B->xfrc_applied || B->d_model_env); }
 static int fail_applied() {
-  return fail(MJL_ERR_UNSUPPORTED, "step VJP / record / replay with applied forces attached: detach them "
-                                   "(mjl_batch_attach_applied(batch, NULL, NULL)) first");
+  return fail(MJL_ERR_UNSUPPORTED, "step VJP / record / replay with applied forces attached or per-env model "
+                                   "parameters on: detach them (mjl_batch_attach_applied(batch, NULL, NULL)) and "
+                                   "set MJL_OPT_PER_ENV_MODEL to 0 first");
 }
 
 template <bool ENV, int TM = 0> static int launch_vjp(mjlBatch* B, const VjpArgs& V0, void* stream,

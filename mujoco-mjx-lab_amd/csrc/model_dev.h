@@ -131,10 +131,23 @@ struct ModelF {
   FrameRec frec[64];
 };
 
+// The size MJL_OPT_PER_ENV_MODEL allocates per env is stated in include/mjx355.h, README.md, INTEGRATION.md and
+// DESIGN.md ("Per-env model parameters"): a change of ModelF changes those figures with this one.
+static_assert(sizeof(ModelF) == 45936, "sizeof(ModelF) is documented: update the figures named above");
+
 // MODE_APPLIED: a flag on MODE_FORWARD / MODE_STEP / MODE_ENV_STEP in step_kernel's template argument, the
 // instantiations that read the applied forces (KParams::qfrc_applied / xfrc_applied)
+// MODE_PER_ENV: a flag beside it, on those three and on MODE_ENV_RESET: env e reads the model block
+// KParams::m_env[e] (MJL_OPT_PER_ENV_MODEL) instead of KParams::m
 enum Mode { MODE_FORWARD = 0, MODE_STEP = 1, MODE_SPEEDTEST = 2, MODE_ENV_STEP = 3, MODE_ENV_RESET = 4,
-            MODE_APPLIED = 8 };
+            MODE_APPLIED = 8, MODE_PER_ENV = 16 };
+
+// What the per-env model builder (model_params_kernel) needs and ModelF does not hold: built on the host by
+// model_param_stage (model_host.h), one per batch on the device.
+struct ParamStage {
+  double impratio;
+  double tran[MJL_MAXPAIR];  // body_invweight0[b1][0] + body_invweight0[b2][0] of the pair's bodies
+};
 
 // per-env state rows, [nenv, dim] each
 struct StateBuf {
@@ -189,6 +202,8 @@ struct KParams {
   // applied forces (mjl_batch_attach_applied), read by the MODE_APPLIED instantiations only
   const float* qfrc_applied;  // [nenv, nv] or null
   const float* xfrc_applied;  // [nenv, nbody, 6] world-frame (force, torque) at xipos, or null
+  // per-env model blocks (MJL_OPT_PER_ENV_MODEL), read by the MODE_PER_ENV instantiations only
+  const ModelF* m_env;  // [nenv] or null
 };
 
 }  // namespace mjl

@@ -305,4 +305,29 @@ inline int model_build(const mjlModelDesc* d, ModelF& f, int& nefc_max, int& nco
   return MJL_OK;
 }
 
+// The staging block of the per-env model builder (model_params_kernel): the two inputs of PairRec.invweight
+// above that ModelF does not keep, in double and by the same expressions, so that the kernel's
+//   (tran + mu * mu * tran) * 2 * mu * mu / impratio
+// rounds to the float model_build stores. `d` has passed model_check (a model that was created).
+inline void model_param_stage(const mjlModelDesc* d, ParamStage& s) {
+  std::memset(&s, 0, sizeof(s));
+  s.impratio = d->impratio;
+  for (int p = 0; p < d->npair; p++) {
+    const int b1 = d->geom_bodyid[d->pair_geom1[p]], b2 = d->geom_bodyid[d->pair_geom2[p]];
+    s.tran[p] = d->body_invweight0[b1][0] + d->body_invweight0[b2][0];
+  }
+}
+
+// dim of a per-env parameter row (MJL_MP_*), -1 for an unknown id
+inline int model_param_dim(const mjlModelDesc* d, int param) {
+  switch (param) {
+    case MJL_MP_BODY_MASS: return d->nbody;
+    case MJL_MP_BODY_INERTIA: return d->nbody * 6;
+    case MJL_MP_DOF_DAMPING: case MJL_MP_DOF_ARMATURE: return d->nv;
+    case MJL_MP_ACTUATOR_GEAR: return d->nu;
+    case MJL_MP_PAIR_FRICTION: return d->npair;
+  }
+  return -1;
+}
+
 }  // namespace mjl

@@ -2727,11 +2727,18 @@ template <class D, bool AUX, class SB> INL void store_step_state(SB& S, LDSA WS<
 // without them. The flag rides in the mode so that the plain instantiations keep their names (the
 // profiler names in bench.py and tools/) and their body: moving the body into a function shared by two
 // kernels changed the register allocation of every existing instantiation.
+//
+// | MODE_PER_ENV (MJL_OPT_PER_ENV_MODEL): env e reads the model block P.m_env[e] instead of P.m. The pointer is
+// as wave-uniform as P.m (one wave = one env), so the model reads stay scalar loads; env_reset, rs_load and
+// the phases take `m` as they do from a shared block. Instantiated with MODE_APPLIED for forward, step and
+// env step (null force buffers are the plain computation, bit for bit) and alone for the reset.
 template <class D, int MODE_, int MW = MJL_MINWAVES> __global__ __launch_bounds__(64, MW) void step_kernel(KParams P) {
-  constexpr int MODE = MODE_ & ~MODE_APPLIED;
+  constexpr int MODE = MODE_ & ~(MODE_APPLIED | MODE_PER_ENV);
   constexpr bool APPLIED = (MODE_ & MODE_APPLIED) != 0;
+  constexpr bool PER_ENV = (MODE_ & MODE_PER_ENV) != 0;
   static_assert(!APPLIED || MODE == MODE_FORWARD || MODE == MODE_STEP || MODE == MODE_ENV_STEP,
                 "applied forces: forward, step and env step");
+  static_assert(!PER_ENV || MODE != MODE_SPEEDTEST, "the speed test runs the shared model");
   __shared__ WS<D> Ws;
   __shared__ float aux_s[MJL_AUX_DIM + 3];
   LDSA WS<D>* W = (LDSA WS<D>*)&Ws;
@@ -2740,6 +2747,7 @@ template <class D, int MODE_, int MW = MJL_MINWAVES> __global__ __launch_bounds_
   const int env = block_env();
   const int lane = threadIdx.x;
   if (env >= P.nenv) return;
+  if constexpr (PER_ENV) m = uniform_ptr((MP)(P.m_env + env));
   if ((MODE == MODE_FORWARD || MODE == MODE_ENV_RESET) && P.mask && !(P.mask[env] > 0.5f)) return;
   if (MODE == MODE_ENV_RESET && P.pool_slot >= 0) {  // reset-pool fill: slot pool_slot of this env
     const int n = min(*P.pool_n, P.pool_slots);
@@ -2876,6 +2884,119 @@ __global__ void env_push_kernel(PushArgs A) {
     for (int i = 2; i < 6; i++) row[i] = 0.f;
   }
   A.timer[2 * e] = left; A.timer[2 * e + 1] = to_next;
+}
+
+// ---------------------------------------------------------------------------------------------
+// per-env model blocks (MJL_OPT_PER_ENV_MODEL): one wavefront per env builds / patches the env's block
+// ---------------------------------------------------------------------------------------------
+// The rule: env e's block is byte for byte what model_build (model_host.h) makes of the descriptor with env
+// e's values substituted. So every home of a field is written (DofRec.damping and the flat dof_damping) and
+// everything model_build derives from one is derived again, by its expressions in its order: body_rootmass
+// (float sum over the subtree, in body order), any_damping, PairRec.invweight (in double, from the staged
+// tran and impratio, every operation rounded on its own as the host rounds it: pair_invweight_rn).
+//
+// a / b correctly rounded. The library is built with -fapprox-func, under which the compiler lowers a double
+// `/` to a reciprocal with Newton steps (no final correction: not correctly rounded), and the toolchain's
+// __ddiv_rn is that same `/`. This is the sequence the compiler emits for an IEEE divide without the flag:
+// both operands scaled, the reciprocal refined twice, the quotient corrected once, the scaling undone. The
+// fused multiply-adds are the algorithm's own.
+INL double div_rn_f64(double num, double den) {
+  bool vcc, unused;
+  const double ds = __builtin_amdgcn_div_scale(num, den, false, &unused);
+  const double ns = __builtin_amdgcn_div_scale(num, den, true, &vcc);
+  double r = __builtin_amdgcn_rcp(ds);
+  r = __builtin_fma(__builtin_fma(-ds, r, 1.0), r, r);
+  r = __builtin_fma(__builtin_fma(-ds, r, 1.0), r, r);
+  const double q = ns * r;
+  const double t = __builtin_fma(-ds, q, ns);
+  return __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(t, r, q, vcc), den, num);
+}
+// model_build's `iw = tran + mu * mu * tran; (float)(iw * 2 * mu * mu / impratio)` with the host's roundings:
+// contraction is switched off in this body (the build's default would fuse tran + (mu * mu) * tran into one
+// multiply-add with a single rounding; the toolchain's __dmul_rn / __dadd_rn are plain `*` / `+` and do not
+// prevent that), and the divide is div_rn_f64. Checked in the `make asm` output: v_mul, v_mul, v_add, v_add
+// (the exact * 2), v_mul, v_mul, then the full divide; no multiply-add on tran.
+INL float pair_invweight_rn(double tran, double mu, double impratio) {
+#pragma clang fp contract(off)
+  const double iw = tran + mu * mu * tran;
+  return (float)div_rn_f64(iw * 2 * mu * mu, impratio);
+}
+struct ModelParamArgs {
+  const ModelF* nominal;  // the batch's shared block: sizes, tree and the fill's source
+  ModelF* blocks;         // [nenv]
+  const ParamStage* stage;
+  const float* v[MJL_NMP];  // [nenv, dim] each, or null = keep
+  const float* mask;        // [nenv] or null
+  int nenv, fill;           // fill: copy the nominal block into every env's (no values, mask ignored)
+};
+__global__ __launch_bounds__(64) void model_params_kernel(ModelParamArgs A) {
+  const int env = blockIdx.x, lane = threadIdx.x;
+  if (env >= A.nenv) return;
+  ModelF* f = A.blocks + env;
+  if (A.fill) {
+    static_assert(sizeof(ModelF) % 16 == 0, "blocks are copied as b128 rows");
+    const u32x4* src = (const u32x4*)A.nominal;
+    u32x4* dst = (u32x4*)f;
+    for (int i = lane; i < (int)(sizeof(ModelF) / 16); i += 64) dst[i] = src[i];
+    return;
+  }
+  if (A.mask && !(A.mask[env] > 0.5f)) return;
+  const ModelF* nom = A.nominal;
+  const int nb = nom->nbody, nv = nom->nv, nu = nom->nu, npair = nom->npair;
+  if (const float* v = A.v[MJL_MP_BODY_MASS]) {
+    const float mass = lane < nb ? v[(size_t)env * nb + lane] : 0.f;
+    const int end = lane < nb ? nom->brec[lane].subtree_end : 0;
+    float mr = 0.f;
+    for (int c = 0; c < nb; c++) {  // every lane takes part in the shuffle; lane b adds its subtree [b, end)
+      const float x = __shfl(mass, c);
+      if (c >= lane && c < end) mr += x;
+    }
+    if (lane < nb) {
+      f->brec[lane].mass = mass;
+      if (lane > 0) f->body_rootmass[lane] = mr;
+    }
+  }
+  if (const float* v = A.v[MJL_MP_BODY_INERTIA])
+    for (int i = lane; i < nb * 6; i += 64) f->brec[i / 6].inertia[i % 6] = v[(size_t)env * nb * 6 + i];
+  if (const float* v = A.v[MJL_MP_DOF_DAMPING]) {
+    const float dmp = lane < nv ? v[(size_t)env * nv + lane] : 0.f;
+    const bool any = __ballot(lane < nv && dmp > 0.f) != 0ull;
+    if (lane < nv) { f->drec[lane].damping = dmp; f->dof_damping[lane] = dmp; }
+    if (lane == 0) f->any_damping = any ? 1 : 0;
+  }
+  if (const float* v = A.v[MJL_MP_DOF_ARMATURE])
+    if (lane < nv) f->drec[lane].armature = v[(size_t)env * nv + lane];
+  if (const float* v = A.v[MJL_MP_ACTUATOR_GEAR])
+    if (lane < nu) f->actuator_gear[lane] = v[(size_t)env * nu + lane];
+  if (const float* v = A.v[MJL_MP_PAIR_FRICTION]) {
+    const double impratio = A.stage->impratio;
+    for (int p = lane; p < npair; p += 64) {
+      const float muf = v[(size_t)env * npair + p];
+      const double tran = A.stage->tran[p], mu = (double)muf;
+      float iw = (float)tran;  // condim 1
+      if (nom->prec[p].condim != 1) iw = pair_invweight_rn(tran, mu, impratio);
+      f->prec[p].mu = muf;
+      f->prec[p].invweight = iw;
+    }
+  }
+}
+
+// field `param` of every env's block -> dst [nenv, dim]
+__global__ void model_params_get_kernel(const ModelF* blocks, int param, int nenv, int dim, float* dst) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)nenv * dim) return;
+  const ModelF* f = blocks + t / dim;
+  const int k = (int)(t % dim);
+  float x;
+  switch (param) {
+    case MJL_MP_BODY_MASS: x = f->brec[k].mass; break;
+    case MJL_MP_BODY_INERTIA: x = f->brec[k / 6].inertia[k % 6]; break;
+    case MJL_MP_DOF_DAMPING: x = f->drec[k].damping; break;
+    case MJL_MP_DOF_ARMATURE: x = f->drec[k].armature; break;
+    case MJL_MP_ACTUATOR_GEAR: x = f->actuator_gear[k]; break;
+    default: x = f->prec[k].mu; break;
+  }
+  dst[t] = x;
 }
 
 }  // namespace mjl

@@ -19,6 +19,9 @@ globals().update({k[4:]: v for k, v in _E.items() if k.startswith("MJL_OPT_")})
 # per-env fields of mjl_get / mjl_set by lower-case name ("qpos": MJL_FIELD_QPOS, ...)
 FIELD = {k[10:].lower(): v for k, v in _E.items() if k.startswith("MJL_FIELD_")}
 
+# per-env model parameters of mjl_batch_set_model_params by field name ("body_mass": MJL_MP_BODY_MASS, ...)
+MODEL_PARAM = {k[7:].lower(): v for k, v in _E.items() if k.startswith("MJL_MP_")}
+
 # exponent-carried cotangents (mjl_vjp_scale_attach): log2 of the output magnitude from which an env's
 # cotangents are rescaled, and the range the library accepts
 VJP_SCALE_THRESHOLD_LOG2 = 40

@@ -102,6 +102,19 @@ class HumanoidEnv:
                                  _ptr(done), self.seed, self.counter + 1 if counter is None else int(counter),
                                  _ptr(noise), _stream()))
 
+    def enable_model_params(self, on: bool = True):
+        """Per-env model blocks for this env's batch (Data.enable_model_params); outside stream capture."""
+        self.data.enable_model_params(on)
+
+    def set_model_params(self, mask: Optional[torch.Tensor] = None, **fields: Optional[torch.Tensor]):
+        """Per-env model parameters (Data.set_model_params): step(), its auto-resets, reset() and the pooled
+        resets run env e on its own body_mass / body_inertia / dof_damping / dof_armature / actuator_gear /
+        pair_friction. Pooled resets are computed with the values at fill_reset_pool()."""
+        self.data.set_model_params(mask, **fields)
+
+    def get_model_params(self, name: str) -> torch.Tensor:
+        return self.data.get_model_params(name)
+
     def _next_counter(self) -> int:
         self.counter += 1
         return self.counter

@@ -138,6 +138,50 @@ class Data:
     def detach_applied(self):
         self.attach_applied(None, None)
 
+    def enable_model_params(self, on: bool = True):
+        """Give every env a model block of its own (MJL_OPT_PER_ENV_MODEL; nenv x ~46 KB), filled with the
+        model's values; False frees them. Outside stream capture. While on, forward, forward_contacts, step,
+        the env step and the resets run env e on its block, the speed test on the model's, and the step VJPs
+        raise."""
+        self.set_option(abi.OPT_PER_ENV_MODEL, int(bool(on)))
+
+    def set_model_params(self, mask: Optional[torch.Tensor] = None, **fields: Optional[torch.Tensor]):
+        """Per-env model parameters (domain randomisation; jax.vmap over a model with batched fields):
+        body_mass [nenv, nbody], body_inertia [nenv, nbody, 6], dof_damping / dof_armature [nenv, nv],
+        actuator_gear [nenv, nu], pair_friction [nenv, npair] as float32 tensors on the batch's device. A
+        field left out (or None) keeps every env's current value; envs with mask <= 0.5 keep their block.
+        One launch, capturable; the tensors are read at execution time and no reference to them or to the mask
+        is kept here: an eager call is ordered on the current stream like any torch op, but a caller that
+        captures the call in a graph keeps the value tensors (and the float32 device mask it passed) alive for
+        as long as the graph is replayed, and updates them in place. See include/mjx355.h
+        mjl_batch_set_model_params for what follows a replaced field and what stays the model's."""
+        unknown = set(fields) - set(abi.MODEL_PARAM)
+        if unknown:
+            raise MjlError(f"unknown model parameter {sorted(unknown)} (known: {sorted(abi.MODEL_PARAM)})")
+        table = (C.c_void_p * abi.NMP)()
+        for name, t in fields.items():
+            if t is None:
+                continue
+            dim = self.model_param_dim(name)
+            if t.numel() != self.nenv * dim:
+                raise MjlError(f"{name} must have {self.nenv} x {dim} elements")
+            if t.device != self.device:
+                raise MjlError(f"{name} must live on {self.device}")
+            table[abi.MODEL_PARAM[name]] = _ptr(t).value
+        mk = None if mask is None else mask.to(device=self.device, dtype=torch.float32).contiguous()
+        check(lib().mjl_batch_set_model_params(self._h, table, _ptr(mk), _stream()))
+
+    def model_param_dim(self, name: str) -> int:
+        return int(lib().mjl_model_param_dim(self.model.handle, abi.MODEL_PARAM[name]))
+
+    def get_model_params(self, name: str) -> torch.Tensor:
+        """Field `name` of every env's model block, [nenv, dim]: what the kernels will use."""
+        out = torch.empty((self.nenv, self.model_param_dim(name)), dtype=torch.float32, device=self.device)
+        if out.numel() == 0:
+            return out
+        check(lib().mjl_batch_get_model_params(self._h, abi.MODEL_PARAM[name], _ptr(out), _stream()))
+        return out.view(self.nenv, self.model.nbody, 6) if name == "body_inertia" else out
+
     def __getattr__(self, name):
         if name in _FIELD_DIM:
             return self.get(name)

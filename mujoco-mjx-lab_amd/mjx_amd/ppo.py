@@ -1213,7 +1213,8 @@ class PPOTrainer:
 
     def __init__(self, cfg, env, eval_env=None, device="cuda", dist=None, out_dir: Optional[str] = None,
                  use_graph: bool = True, jax_keys: bool = False, fused_policy: bool = True,
-                 reset_pool: int = 16, update_graph: bool = True, push: Optional[dict] = None):
+                 reset_pool: int = 16, update_graph: bool = True, push: Optional[dict] = None,
+                 randomize: Optional[dict] = None):
         """jax_keys: draw every env reset (initial, auto-reset, eval) from the jax.random key chain
         train_ppo.py derives from cfg.seed (:88-118, :132/:150-151 per rollout step, :325, :359,
         :419, eval :268-293), so the reset stream equals the reference's for the same seed.
@@ -1227,7 +1228,11 @@ class PPOTrainer:
         iteration on.
         push: random pushes on the training envs (HumanoidEnv.push's body / interval / duration / force),
         one launch before each rollout step, inside the captured rollout; None (default): nothing is
-        attached and the rollout is launch for launch what it was. Evaluation envs are never pushed."""
+        attached and the rollout is launch for launch what it was. Evaluation envs are never pushed.
+        randomize: domain randomisation of the training envs: scale ranges {"mass" | "friction" | "damping" |
+        "armature" | "gear": (lo, hi)} (randomize.draw_model_params), drawn once here, before the first
+        reset, from cfg.seed and the rank; None or empty (default): no option is set and no new kernel runs.
+        Evaluation envs keep the model's values."""
         self.cfg, self.env, self.eval_env, self.dist = cfg, env, eval_env, dist
         self.rank = dist.get_rank() if dist is not None else 0
         self.world = dist.get_world_size() if dist is not None else 1
@@ -1250,6 +1255,16 @@ class PPOTrainer:
         self.jax_keys = bool(jax_keys) and self.device.type == "cuda" and hasattr(env, "set_reset_keys")
         if self.jax_keys:
             self._jax_init()
+        self.randomize = None
+        if randomize:
+            if not hasattr(env, "set_model_params"):
+                raise ValueError("randomize needs an env with per-env model parameters (HumanoidEnv)")
+            from .randomize import draw_model_params
+            self.randomize = dict(randomize)
+            draw = draw_model_params(env.sys.m, env.num_envs, self.randomize, seed=int(cfg.seed) * 7919 + self.rank)
+            self.model_params = {k: v.to(self.device) for k, v in draw.items()}
+            env.enable_model_params()
+            env.set_model_params(**self.model_params)
         self.obs = env.reset().clone()
         self.use_graph = bool(use_graph)
         self._buf, self._graph, self._rollouts = None, None, 0

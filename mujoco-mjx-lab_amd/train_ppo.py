@@ -41,6 +41,13 @@ def parse_args(argv=None):
                     help="env steps between pushes, drawn per env (default 100 200)")
     ap.add_argument("--push-duration", type=int, default=None, metavar="K", help="env steps a push lasts (default 5)")
     ap.add_argument("--push-body", default=None, metavar="NAME", help="pushed body (default: the env's pelvis body)")
+    for name, what in (("mass", "body masses (inertias scale with them), one scale per body"),
+                       ("friction", "sliding friction, one scale per geom (a pair takes the larger scaled value)"),
+                       ("damping", "joint damping, one scale per dof"), ("armature", "armature, one scale per dof"),
+                       ("gear", "actuator gear, one scale per actuator")):
+        ap.add_argument(f"--rand-{name}", type=float, nargs=2, metavar=("LO", "HI"), default=None,
+                        help=f"domain randomisation of the training envs: {what}, uniform in [LO, HI] times the "
+                             "model's value, drawn once at start (off by default)")
     a = ap.parse_args(argv)
     if a.push_force is None and (a.push_interval or a.push_duration is not None or a.push_body):
         ap.error("--push-interval / --push-duration / --push-body need --push-force LO HI")
@@ -56,6 +63,13 @@ def push_config(a, model, env_cfg):
         raise SystemExit(f"--push-body: no body named {a.push_body!r}")
     return {"body": body, "interval": tuple(a.push_interval or (100, 200)),
             "duration": 5 if a.push_duration is None else a.push_duration, "force": tuple(a.push_force)}
+
+
+def randomize_config(a):
+    """PPOTrainer's `randomize` from the --rand-* flags: None when none is given (no option set, no new kernel)."""
+    r = {k: tuple(getattr(a, "rand_" + k)) for k in ("mass", "friction", "damping", "armature", "gear")
+         if getattr(a, "rand_" + k) is not None}
+    return r or None
 
 
 def main():
@@ -91,7 +105,7 @@ def main():
     if rank == 0:
         out = os.path.join(cfg.results_dir, time.strftime("%Y%m%d_%H%M%S") + "_ppo")
     tr = PPOTrainer(cfg, env, eval_env, device=f"cuda:{local}", dist=dist, out_dir=out, jax_keys=a.jax_keys,
-                    push=push_config(a, model, env_cfg))
+                    push=push_config(a, model, env_cfg), randomize=randomize_config(a))
     tr.train()
     if dist is not None:
         dist.destroy_process_group()
