@@ -54,6 +54,7 @@ enum { MJL_INT_EULER = 0, MJL_INT_IMPLICITFAST = 3 };
 enum { MJL_COL_PLANE_SPHERE = 0, MJL_COL_PLANE_CAPSULE = 1, MJL_COL_SPHERE_SPHERE = 2,
        MJL_COL_SPHERE_CAPSULE = 3, MJL_COL_CAPSULE_CAPSULE = 4 };
 enum { MJL_SENS_TOUCH = 0 };
+enum { MJL_ACT_MOTOR = 0, MJL_ACT_GENERAL = 1 };
 
 typedef struct mjlModelDesc {
   int32_t nq, nv, nu, nbody, njnt, ngeom, nsite, ntendon, npair, nsensor, nsensordata;
@@ -91,6 +92,15 @@ typedef struct mjlModelDesc {
 
   int32_t actuator_trnid[MJL_MAXU], actuator_ctrllimited[MJL_MAXU];
   double actuator_gear[MJL_MAXU], actuator_ctrlrange[MJL_MAXU][2];
+  /* General (stateless, affine-bias) actuators on a hinge, MJX forward.fwd_actuation with joint transmission:
+   *   force = gain * clip(ctrl) + biasprm[0] + biasprm[1] * gear * qpos[j] + biasprm[2] * gear * qvel[d],
+   * clipped to forcerange when forcelimited, and qfrc_actuator[d] += gear * force. Under implicitfast the
+   * integrator's matrix gets -dt * gear^2 * biasprm[2] on dof d's diagonal, whether or not the force was
+   * clipped (derivative.deriv_smooth_vel). actuator_kind: MJL_ACT_MOTOR (0) reads none of the four fields
+   * below (gain 1, no bias, no force limit), so an all-zero group is the torque motor; MJL_ACT_GENERAL reads
+   * them all. Not differentiated: see the step VJP entries. */
+  int32_t actuator_kind[MJL_MAXU], actuator_forcelimited[MJL_MAXU];
+  double actuator_gain[MJL_MAXU], actuator_biasprm[MJL_MAXU][3], actuator_forcerange[MJL_MAXU][2];
 
   int32_t tendon_num[MJL_MAXTENDON], tendon_jnt[MJL_MAXTENDON][MJL_MAXTENWRAP];
   int32_t tendon_limited[MJL_MAXTENDON];
@@ -185,7 +195,7 @@ int mjl_batch_nenv(const mjlBatch* batch);
  * MJL_OPT_RESET_POOL (default 0): value = slots per env (<= 64) of the reset pool that
  * mjl_env_fill_reset_pool fills (call outside stream capture; 0 frees it).
  * MJL_OPT_PER_ENV_MODEL (default 0): 1 gives every env a model block of its own, filled with the
- * model's values (nenv x 45936 bytes, the size of one device model block: 94 MB for 2048 envs; call
+ * model's values (nenv x 46976 bytes, the size of one device model block: 96 MB for 2048 envs; call
  * outside stream capture; 0 frees them). See mjl_batch_set_model_params. */
 enum { MJL_OPT_STORE_DERIVED = 0, MJL_OPT_FORCE_GLOBAL_ROWS = 1, MJL_OPT_VJP_UNROLLED = 2, MJL_OPT_RESET_POOL = 3,
        MJL_OPT_VJP_TAPE = 4, MJL_OPT_PER_ENV_MODEL = 5 };

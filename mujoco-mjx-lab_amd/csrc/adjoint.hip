@@ -2004,7 +2004,7 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
   SYNC();
   // ---- forward (forward() + integrate(), rows in the env's global slab)
   STAMP(0, lane);
-  smooth_forward<D, false>(m, W, lane, kin_prefetch(m, lane));
+  smooth_forward<D, false, false, false>(m, W, lane, kin_prefetch(m, lane));
   SYNC();
   if constexpr (TM == 1) {  // unrolled CG: chol(M) -- the reverse sweep's preconditioner -- in the slot's Lc
     if (unr && m->solver != MJL_SOLVER_NEWTON) {
@@ -2027,7 +2027,7 @@ __global__ __launch_bounds__(64, LEAN ? 2 : 1) void vjp_kernel(KParams P, VjpArg
     chol_factor_solve<D>(W->H, A->Lc, A->invdc, nv, W->frc_smooth, lane);
     SYNC();
   }
-  integrate<D>(m, W, lane, A->ap);
+  integrate<D, false>(m, W, lane, A->ap);
   STAMP(1, lane);
   if constexpr (TM == 1) {  // record: the workspace as the reverse passes find it, then the env step
     {
@@ -2290,7 +2290,7 @@ __global__ __launch_bounds__(64, 2) void vjp_record_kernel(KParams P, VjpArgs V)
   }
   SYNC();
   STAMP(0, lane);
-  smooth_forward<DL, false>(m, W, lane, kin_prefetch(m, lane));
+  smooth_forward<DL, false, false, false>(m, W, lane, kin_prefetch(m, lane));
   SYNC();
   SolveTape tp;  // (UNR)
   if constexpr (UNR) {
@@ -2339,7 +2339,7 @@ __global__ __launch_bounds__(64, 2) void vjp_record_kernel(KParams P, VjpArgs V)
     chol_factor_solve<DL>(W->H, ab + 2 * LD, ab + LD, nv, W->frc_smooth, lane);
     SYNC();
   }
-  integrate<DL>(m, W, lane, ab);
+  integrate<DL, false>(m, W, lane, ab);
   STAMP(1, lane);
   SYNC();
   static_assert(SA::invdc == SA::ap + LD && SA::Lc == SA::ap + 2 * LD, "a', 1/diag and the factor are contiguous in the slot, as in ab");

@@ -707,8 +707,15 @@ int mjl_env_reset(mjlBatch* B, const float* mask, uint64_t seed, uint64_t counte
 // The adjoint of J(q)' w with respect to q is not built: every VJP, record and replay entry checks this
 // before anything else, so a batch with applied forces attached is refused whatever the other arguments.
 // Nor are the adjoints through per-env model blocks: the same entries refuse a batch with MJL_OPT_PER_ENV_MODEL on.
-static bool applied_attached(const mjlBatch* B) { return B && (B->qfrc_applied || B->xfrc_applied || B->d_model_env); }
-static int fail_applied() {
+// Nor is the adjoint of a general actuator's force (its qpos and qvel terms, its clip): a model with any
+// non-motor actuator is refused by the same entries, with a message of its own.
+static bool applied_attached(const mjlBatch* B) {
+  return B && (B->qfrc_applied || B->xfrc_applied || B->d_model_env || B->model->mf.act_general);
+}
+static int fail_applied(const mjlBatch* B) {
+  if (B->model->mf.act_general)
+    return fail(MJL_ERR_UNSUPPORTED, "step VJP / record / replay on a model with non-motor (general) actuators: "
+                                     "general actuators are not differentiated");
   return fail(MJL_ERR_UNSUPPORTED, "step VJP / record / replay with applied forces attached or per-env model "
                                    "parameters on: detach them (mjl_batch_attach_applied(batch, NULL, NULL)) and "
                                    "set MJL_OPT_PER_ENV_MODEL to 0 first");
@@ -818,7 +825,7 @@ static VjpArgs record_io(mjlBatch* B, float* slot, const float* act, float* obs,
 
 // the env-step VJPs: the recompute (TM 0) or the replay of tape slot `slot` (TM 2)
 template <int TM> static int env_vjp(mjlBatch* B, int slot, VjpArgs V, void* stream) {
-  if (applied_attached(B)) return fail_applied();
+  if (applied_attached(B)) return fail_applied(B);
   if (!B || !V.act || !V.g_qpos || !V.g_qvel || !V.g_rew || !V.g_aux || !V.o_qpos || !V.o_qvel || !V.o_ctrl || !V.o_aux)
     return fail(MJL_ERR_ARG, "bad argument");
   if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
@@ -849,7 +856,7 @@ int mjl_env_step_vjp_guarded(mjlBatch* B, const float* act, const float* g_qpos,
 
 int mjl_step_vjp_full(mjlBatch* B, const float* g_qpos, const float* g_qvel, const float* g_qacc_ws,
                       float* out_qpos, float* out_qvel, float* out_qacc_ws, float* out_ctrl, void* stream) {
-  if (applied_attached(B)) return fail_applied();
+  if (applied_attached(B)) return fail_applied(B);
   if (!B || !g_qpos || !g_qvel || !out_qpos || !out_qvel || !out_ctrl) return fail(MJL_ERR_ARG, "bad argument");
   return launch_vjp<false>(B, vjp_io(nullptr, g_qpos, g_qvel, g_qacc_ws, nullptr, nullptr, out_qpos, out_qvel,
                                      out_qacc_ws, out_ctrl, nullptr, nullptr), stream);
@@ -865,7 +872,7 @@ int mjl_env_step_vjp_full(mjlBatch* B, const float* act, const float* g_qpos, co
 
 int mjl_env_step_record(mjlBatch* B, int slot, const float* act, float* obs, float* rew, float* term, float* trunc,
                         void* stream) {
-  if (applied_attached(B)) return fail_applied();
+  if (applied_attached(B)) return fail_applied(B);
   if (!B || !act || !obs || !rew || !term || !trunc) return fail(MJL_ERR_ARG, "bad argument");
   if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
   float* const sp = tape_slot(B, slot);
@@ -877,7 +884,7 @@ int mjl_env_step_record(mjlBatch* B, int slot, const float* act, float* obs, flo
 int mjl_env_step_record_apg(mjlBatch* B, int slot, const float* act, float* obs, float* rew, float* term, float* trunc,
                             float gamma, float diverge_qvel, uint8_t* alive, float* disc, float* ret, float* dropped,
                             float* grew, float* rfin, void* stream) {
-  if (applied_attached(B)) return fail_applied();
+  if (applied_attached(B)) return fail_applied(B);
   if (!B || !act || !obs || !rew || !term || !trunc || !alive || !disc || !ret || !dropped || !grew || !rfin)
     return fail(MJL_ERR_ARG, "bad argument");
   if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
@@ -1275,7 +1282,7 @@ extern "C" int mjl_env_step_record_apg_next(mjlBatch* B, int slot, const float* 
                                  float* dropped, float* grew, float* rfin, const float* mean, const float* var,
                                  int use_norm, float* o, float* on, uint8_t* alive_snap, int nl, const int* widths,
                                  const float* const* w_t, const float* const* b, float* const* ys, void* stream) {
-  if (applied_attached(B)) return fail_applied();
+  if (applied_attached(B)) return fail_applied(B);
   if (!B || !act || !obs || !rew || !term || !trunc || !alive || !disc || !ret || !dropped || !grew || !rfin || !o ||
       !on || !alive_snap || (use_norm && (!mean || !var)))
     return fail(MJL_ERR_ARG, "bad argument");
@@ -1303,7 +1310,7 @@ extern "C" int mjl_env_step_vjp_replay_apg(mjlBatch* B, int slot, const float* a
                                            const int* widths, const float* const* w, float* const* ys, const float* o,
                                            const uint8_t* alive_snap, const float* mean, const float* var,
                                            int use_norm, void* stream) {
-  if (applied_attached(B)) return fail_applied();
+  if (applied_attached(B)) return fail_applied(B);
   if (!B || !act || !g_qpos || !g_qvel || !g_rew || !g_aux || !out_qpos || !out_qvel || !out_act || !out_aux || !o ||
       !alive_snap || !w || !w[0] || (use_norm && (!mean || !var)))
     return fail(MJL_ERR_ARG, "bad argument");

@@ -2,6 +2,7 @@
 // Built on the host from mjlModelDesc (include/mjx355.h) by model_build (model_host.h); lives in device
 // global memory, read through the scalar/vector caches (a few KB, shared by every env).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/mjx355.h"
@@ -58,6 +59,16 @@ struct alignas(16) LimRec {
   int on, qadr, dofadr, pad;  // on: the joint / tendon is a limit-row candidate
   float lo, hi, margin, invweight;
   float solref[2], solimp[5], pad1;
+};
+
+// a general actuator (MJL_ACT_GENERAL; a motor of a model that has one is written as gain 1, no bias, no limit):
+// force = gain * clip(ctrl) + b0 + b1 * gear * qpos[qadr] + b2 * gear * qvel[dof], clipped to [flo, fhi] when
+// flim; gear, the dof and the ctrl range stay in the flat actuator_* members (one home: a per-env gear is
+// followed by length, velocity, moment and the integrator's gear^2 * b2 without any derived copy)
+struct alignas(16) ActRec {
+  float gain, b0, b1, b2;
+  float flo, fhi;
+  int flim, qadr;
 };
 
 // ModelF holds exactly what a kernel reads. Host staging does not belong here: a value the kernels take
@@ -129,11 +140,20 @@ struct ModelF {
   LimRec jlim[MJL_MAXJNT], tlim[MJL_MAXTENDON];
   HingeRec bhinge[MJL_MAXBODY][3];
   FrameRec frec[64];
+
+  // General actuators, after everything a motor-only model has: up to here the block of a model without one
+  // is laid out and filled as it always was, and the rest of it is zero.
+  //   act_general  some actuator is MJL_ACT_GENERAL: the actuation phase takes arec (a scalar branch)
+  //   act_b2       some arec[u].b2 != 0: under implicitfast the integrator's matrix gets
+  //                -dt * sum_u gear_u^2 b2_u on the diagonal, also when every dof_damping is 0
+  ActRec arec[MJL_MAXU];
+  int act_general, act_b2, act_pad[2];
 };
 
 // The size MJL_OPT_PER_ENV_MODEL allocates per env is stated in include/mjx355.h, README.md, INTEGRATION.md and
 // DESIGN.md ("Per-env model parameters"): a change of ModelF changes those figures with this one.
-static_assert(sizeof(ModelF) == 45936, "sizeof(ModelF) is documented: update the figures named above");
+static_assert(offsetof(ModelF, arec) == 45936, "the motor-only part of the block keeps its layout");
+static_assert(sizeof(ModelF) == 46976, "sizeof(ModelF) is documented: update the figures named above");
 
 // MODE_APPLIED: a flag on MODE_FORWARD / MODE_STEP / MODE_ENV_STEP in step_kernel's template argument, the
 // instantiations that read the applied forces (KParams::qfrc_applied / xfrc_applied)

@@ -5,6 +5,7 @@
 // flat members straight from the descriptor: one conversion per value, no staging copy; it cannot fail
 // after the check.
 #pragma once
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -110,6 +111,18 @@ inline int model_check(const mjlModelDesc* d, std::string& msg) {
     const int j = d->actuator_trnid[u];
     if (j < 0 || j >= d->njnt || d->jnt_type[j] != MJL_JNT_HINGE)
       return model_err(msg, MJL_ERR_UNSUPPORTED, "actuator %d: only hinge joint transmission supported", u);
+    if (d->actuator_kind[u] != MJL_ACT_MOTOR && d->actuator_kind[u] != MJL_ACT_GENERAL)
+      return model_err(msg, MJL_ERR_UNSUPPORTED, "actuator %d: kind %d not supported (motor, general)", u,
+                       d->actuator_kind[u]);
+    if (d->actuator_kind[u] != MJL_ACT_GENERAL) continue;  // a motor reads none of the general fields
+    const double prm[6] = {d->actuator_gain[u], d->actuator_biasprm[u][0], d->actuator_biasprm[u][1],
+                           d->actuator_biasprm[u][2], d->actuator_forcerange[u][0], d->actuator_forcerange[u][1]};
+    for (double x : prm)
+      if (!std::isfinite(x))
+        return model_err(msg, MJL_ERR_ARG, "actuator %d: gain, biasprm and forcerange must be finite", u);
+    if (d->actuator_forcelimited[u] && d->actuator_forcerange[u][0] > d->actuator_forcerange[u][1])
+      return model_err(msg, MJL_ERR_ARG, "actuator %d: forcerange [%g, %g] is empty", u, d->actuator_forcerange[u][0],
+                       d->actuator_forcerange[u][1]);
   }
   for (int t = 0; t < d->ntendon; t++) {
     MJL_RANGE("tendon_num", t, d->tendon_num[t], 0, MJL_MAXTENWRAP + 1);
@@ -278,6 +291,21 @@ inline int model_build(const mjlModelDesc* d, ModelF& f, int& nefc_max, int& nco
     f.actuator_gear[u] = (float)d->actuator_gear[u];
     f.actuator_ctrlrange[u][0] = (float)d->actuator_ctrlrange[u][0];
     f.actuator_ctrlrange[u][1] = (float)d->actuator_ctrlrange[u][1];
+    f.act_general |= d->actuator_kind[u] == MJL_ACT_GENERAL;
+  }
+  // a model with a general actuator runs them all through arec (its motors as gain 1, no bias, no limit);
+  // a motor-only model leaves arec zero and never reads it
+  for (int u = 0; u < d->nu && f.act_general; u++) {
+    ActRec& r = f.arec[u];
+    r.qadr = d->jnt_qposadr[d->actuator_trnid[u]];
+    r.gain = 1.f;
+    if (d->actuator_kind[u] != MJL_ACT_GENERAL) continue;
+    r.gain = (float)d->actuator_gain[u];
+    r.b0 = (float)d->actuator_biasprm[u][0]; r.b1 = (float)d->actuator_biasprm[u][1];
+    r.b2 = (float)d->actuator_biasprm[u][2];
+    r.flim = d->actuator_forcelimited[u] != 0;
+    r.flo = (float)d->actuator_forcerange[u][0]; r.fhi = (float)d->actuator_forcerange[u][1];
+    f.act_b2 |= r.b2 != 0.f;
   }
 
   for (int t = 0; t < d->ntendon; t++) {

@@ -1069,7 +1069,9 @@ template <class D> PHASE void com_pos_crb(MP m_, LDSA WS<D>* W, int lane, const 
 // scom) x f; f], is what cdof projects: summed over subtrees beside the body forces (same MFMAs, columns
 // 6..11) and projected on cdof a second time, so frc_bias stays Data.qfrc_bias. Its rows live in crb (dead
 // since the mass matrix) and its subtree sums in cinert (dead once this stage's body forces are formed).
-template <class D, bool APPLIED = false>
+// GENERAL: the instantiation can run general actuators (ModelF::act_general). The step VJP / record / replay
+// kernels refuse such models (capi.hip) and instantiate the motor path alone.
+template <class D, bool APPLIED = false, bool GENERAL = true>
 PHASE void velocity_stage(MP m_, LDSA WS<D>* W, int lane, const KinPre& kp, const AppliedRegs* ap = nullptr) {
   MP m = uniform_ptr(m_);
   const int maxlevel = m->maxlevel, nbody = m->nbody, nv = m->nv, nu = m->nu;
@@ -1174,7 +1176,20 @@ PHASE void velocity_stage(MP m_, LDSA WS<D>* W, int lane, const KinPre& kp, cons
   if (lane < D::LD) W->frc_act[lane] = 0.f;
   SYNC();
   TACC(27, tv, lane);
-  if (isu) {  // motors with joint transmission
+  bool general = false;
+  if constexpr (GENERAL) general = m->act_general != 0;
+  if (general) {  // model-uniform (a scalar branch); the record is loaded here, off the motor path
+    // general actuators with joint transmission: force = gain ctrl + b0 + b1 length + b2 velocity, length =
+    // gear qpos, velocity = gear qvel, clipped to the force range   [forward.fwd_actuation]
+    if (isu) {
+      const ActRec ar = ldrec(&m->arec[lane]);
+      float c = W->ctrl[lane];
+      if (ulim) c = fminf(fmaxf(c, ulo), uhi);
+      float force = ar.gain * c + (ar.b0 + ar.b1 * (ugear * W->qpos[ar.qadr]) + ar.b2 * (ugear * W->qvel[udof]));
+      if (ar.flim) force = fminf(fmaxf(force, ar.flo), ar.fhi);
+      atomicAdd((float*)&W->frc_act[udof], ugear * force);
+    }
+  } else if (isu) {  // motors with joint transmission
     float c = W->ctrl[lane];
     if (ulim) c = fminf(fmaxf(c, ulo), uhi);
     atomicAdd((float*)&W->frc_act[udof], ugear * c);
@@ -2227,7 +2242,7 @@ NOINL void global_rows_path(MP m, LDSA WS<D>* W, float* scratch_env, int gmax_ef
 
 // the smooth dynamics: kinematics through qacc_smooth (no barrier after the last store: the caller's, or
 // build_rows', comes before its first read). STAMPS: forward()'s phase stamps of the timing build.
-template <class D, bool STAMPS, bool APPLIED = false>
+template <class D, bool STAMPS, bool APPLIED = false, bool GENERAL = true>
 INL void smooth_forward(MP m, LDSA WS<D>* W, int lane, const KinPre& kp, const AppliedRegs* ap = nullptr) {
   constexpr int LD = D::LD;
   if constexpr (STAMPS) STAMP(0, lane);
@@ -2235,7 +2250,7 @@ INL void smooth_forward(MP m, LDSA WS<D>* W, int lane, const KinPre& kp, const A
   if constexpr (STAMPS) STAMP(1, lane);
   com_pos_crb<D>(m, W, lane, kp);
   if constexpr (STAMPS) STAMP(2, lane);
-  velocity_stage<D, APPLIED>(m, W, lane, kp, ap);
+  velocity_stage<D, APPLIED, GENERAL>(m, W, lane, kp, ap);
   if constexpr (STAMPS) STAMP(3, lane);
   // factor M into H: qacc_smooth now, CG preconditioner later
   float x = chol_factor_solve<D>(W->M, W->H, W->invd, m->nv, W->frc_smooth, lane);
@@ -2266,16 +2281,30 @@ PHASE void forward(MP m_, LDSA WS<D>* W, float* scratch_env, int gmax_efc, int g
 // ---------------------------------------------------------------------------------------------
 // integration (Euler with eulerdamp / implicitfast)   [forward.euler / forward.implicit]
 // ---------------------------------------------------------------------------------------------
-template <class D> PHASE void integrate(MP m_, LDSA WS<D>* W, int lane, LDSA float* ap_out = nullptr) {
+// GENERAL: as velocity_stage's
+template <class D, bool GENERAL = true> PHASE void integrate(MP m_, LDSA WS<D>* W, int lane, LDSA float* ap_out = nullptr) {
   MP m = uniform_ptr(m_);
   constexpr int LD = D::LD;
   const int nv = m->nv;
   const float dt = m->timestep;
   // this lane's joint record and dof damping, issued before the first wait
   const JntRec jr = ldrec(&m->jrec[lane < m->njnt ? lane : 0]);
-  const float dmp = m->dof_damping[(lane & 31) < nv ? (lane & 31) : 0];
+  float dmp = m->dof_damping[(lane & 31) < nv ? (lane & 31) : 0];
   float qa = (lane < nv) ? W->qacc[lane] : 0.f;
   bool damp = (m->integrator == MJL_INT_IMPLICITFAST || m->eulerdamp) && m->any_damping;
+  bool act_b2 = false;
+  if constexpr (GENERAL) act_b2 = m->act_b2 != 0;
+  if (act_b2 && m->integrator == MJL_INT_IMPLICITFAST) {  // model-uniform (a scalar branch)
+    // implicitfast: the actuators' velocity derivative joins the damping, M + dt (diag(damping) - diag(sum_u
+    // gear_u^2 b2_u)), whether or not a force was clipped [derivative.deriv_smooth_vel]; Euler takes the
+    // damping alone. From gear and b2 themselves, in actuator order: a per-env gear needs no derived copy.
+    const int nu = m->nu;
+    for (int u = 0; u < nu; u++) {
+      const float g = m->actuator_gear[u];
+      if (m->actuator_dof[u] == (lane & 31)) dmp -= g * g * m->arec[u].b2;
+    }
+    damp = true;
+  }
   if (damp) {  // (M + dt*diag(damping)) qacc' = qfrc_smooth + qfrc_constraint
     if constexpr (D::NV < 32) {
       // dt*diag(damping) enters the factor as its MFMA-layout addend (register v of lane l holds

@@ -11,6 +11,9 @@ reference humanoid models use (`models/humanoid_mjx.xml`, `models/humanoid.xml`)
 * contype/conaffinity, parent filtering, `<contact><exclude>`, contact-parameter mixing
 * limited hinges (degrees -> radians), armature/damping/stiffness, fixed tendons with limits
 * motors (joint transmission, gear, ctrlrange), touch sensors on box sites, keyframes
+* <position kp kv inheritrange>, <velocity kv>, <general gaintype="fixed" biastype="none|affine"> on hinges
+  (gear, ctrlrange, forcerange, class and per-tag <default>s); dampratio, timeconst, dyntype, other gain /
+  bias types and non-joint transmissions are refused by name
 * `mj_setConst` quantities: qpos0, body/dof/tendon invweight0 and stat.meaninertia
   (computed here with an independent float64 forward pass at qpos0)
 
@@ -231,6 +234,87 @@ class _Defaults:
         attrs = dict(self.classes[cname].get(tag, {}))
         attrs.update({k: v for k, v in el.attrib.items() if k != "class"})
         return attrs
+
+
+# ----------------------------------------------------------------------------------------------
+# general actuators (include/mjx355.h actuator_kind ...): <position>, <velocity>, <general> on a hinge
+# ----------------------------------------------------------------------------------------------
+ACT_MOTOR, ACT_GENERAL = 0, 1
+GENERAL_ACTUATOR_ARRAYS = ("actuator_kind", "actuator_gain", "actuator_biasprm", "actuator_forcelimited",
+                           "actuator_forcerange")
+# refused whatever their value: what they ask for is not built
+_ACT_REFUSED_ATTRS = ("dampratio", "timeconst", "actdim", "actlimited", "actrange", "actearly")
+_ACT_TRANSMISSIONS = ("jointinparent", "tendon", "site", "refsite", "body", "slidersite", "cranksite")
+
+
+def general_actuator_arrays(kind, gain, biasprm, forcelimited, forcerange) -> Dict[str, np.ndarray]:
+    """The five arrays a model with a non-motor actuator carries beside the motors' (one row per actuator)."""
+    return {"actuator_kind": np.array(kind, np.int32), "actuator_gain": np.array(gain, float),
+            "actuator_biasprm": np.array(biasprm, float).reshape(-1, 3),
+            "actuator_forcelimited": np.array(forcelimited, np.int32),
+            "actuator_forcerange": np.array(forcerange, float).reshape(-1, 2)}
+
+
+def _auto_limited(a: Dict[str, str], flag: str, rng: str, tag: str) -> int:
+    v = a.get(flag, "auto")
+    if v not in ("true", "false", "auto"):
+        raise MJCFError(f"<{tag}> {flag}='{v}' not supported")
+    # auto: limited iff a range is given; "0 0" is MuJoCo's "not given" (the built-in default of the motor tag)
+    return int(v == "true" or (v == "auto" and rng in a and any(_floats(a[rng]))))
+
+
+def _general_actuator(a_el, defaults: "_Defaults", jnt_names, joints) -> dict:
+    """One <position> / <velocity> / <general> element as gain, affine bias and limits (MuJoCo's shortcuts:
+    position: gain kp, bias (0, -kp, -kv); velocity: gain kv, bias (0, 0, -kv)). Defaults are kept per tag."""
+    tag = a_el.tag
+    a = defaults.resolve("motor" if tag == "general" else tag, a_el, None)
+    if tag != "general":  # the built-in motor defaults ("ctrlrange 0 0") belong to <motor> / <general>
+        a.setdefault("gear", "1")
+    for name in _ACT_REFUSED_ATTRS:
+        if name in a:
+            raise MJCFError(f"<{tag}> attribute '{name}' not supported")
+    for name in _ACT_TRANSMISSIONS:
+        if name in a:
+            raise MJCFError(f"<{tag}> transmission '{name}' not supported: only joint transmission")
+    if a.get("dyntype", "none") != "none":
+        raise MJCFError(f"<{tag}> dyntype='{a['dyntype']}' not supported (none)")
+    if a.get("gaintype", "fixed") != "fixed":
+        raise MJCFError(f"<{tag}> gaintype='{a['gaintype']}' not supported (fixed)")
+    if a.get("biastype", "none") not in ("none", "affine"):
+        raise MJCFError(f"<{tag}> biastype='{a['biastype']}' not supported (none, affine)")
+    jn = a.get("joint")
+    if jn is None:
+        raise MJCFError(f"<{tag}>: only joint transmission supported")
+    jid = jnt_names.index(jn)
+    if joints[jid]["type"] != JNT_HINGE:
+        raise MJCFError(f"<{tag}> on non-hinge joint not supported")
+    if tag == "position":
+        kp, kv = float(a.get("kp", "1")), float(a.get("kv", "0"))
+        gain, bias = kp, (0.0, -kp, -kv)
+    elif tag == "velocity":
+        kv = float(a.get("kv", "1"))
+        gain, bias = kv, (0.0, 0.0, -kv)
+    else:
+        gain = (_floats(a.get("gainprm", "1")) + [0.0])[0]
+        prm = _floats(a.get("biasprm", "0 0 0"))
+        if any(prm[3:]) or any(_floats(a.get("gainprm", "1"))[1:]):
+            raise MJCFError("<general> gainprm / biasprm: one gain and three bias parameters are supported")
+        bias = tuple((prm + [0.0, 0.0, 0.0])[:3]) if a.get("biastype", "none") == "affine" else (0.0, 0.0, 0.0)
+    cr = _floats(a["ctrlrange"]) if "ctrlrange" in a else [0.0, 0.0]
+    limited = _auto_limited(a, "ctrllimited", "ctrlrange", tag)
+    if tag == "position" and float(a.get("inheritrange", "0")) > 0:
+        if "ctrlrange" in a_el.attrib:
+            raise MJCFError("<position> inheritrange and ctrlrange are exclusive")
+        if not joints[jid]["limited"]:
+            raise MJCFError("<position> inheritrange needs a limited joint")
+        lo, hi = (float(x) for x in joints[jid]["range"])
+        mean, half = 0.5 * (lo + hi), 0.5 * (hi - lo) * float(a["inheritrange"])
+        cr, limited = [mean - half, mean + half], 1
+    elif "inheritrange" in a and tag != "position":
+        raise MJCFError(f"<{tag}> attribute 'inheritrange' not supported")
+    fr = _floats(a["forcerange"]) if "forcerange" in a else [0.0, 0.0]
+    return {"jnt": jid, "gear": _floats(a["gear"])[0], "ctrlrange": cr, "ctrllimited": limited, "gain": gain,
+            "biasprm": bias, "forcelimited": _auto_limited(a, "forcelimited", "forcerange", tag), "forcerange": fr}
 
 
 def _geom_inertia(gtype: int, size, density: float):
@@ -606,6 +690,10 @@ def compile_xml_string(text: str, name_hint: str = "", sha: str = "") -> Compile
     act_names = []
     if act is not None:
         for a_el in act:
+            if a_el.tag in ("position", "velocity", "general"):
+                actuators.append(_general_actuator(a_el, defaults, jnt_names, joints))
+                act_names.append(a_el.get("name", ""))
+                continue
             if a_el.tag != "motor":
                 raise MJCFError(f"actuator <{a_el.tag}> not supported")
             a = defaults.resolve("motor", a_el, None)
@@ -747,6 +835,12 @@ def compile_xml_string(text: str, name_hint: str = "", sha: str = "") -> Compile
     A["actuator_gear"] = np.array([a["gear"] for a in actuators])
     A["actuator_ctrlrange"] = np.array([a["ctrlrange"] for a in actuators]).reshape(-1, 2)
     A["actuator_ctrllimited"] = np.array([a["ctrllimited"] for a in actuators], np.int32)
+    if any("gain" in a for a in actuators):  # a motor-only model carries the arrays it always did
+        A.update(general_actuator_arrays(
+            kind=[ACT_GENERAL if "gain" in a else ACT_MOTOR for a in actuators],
+            gain=[a.get("gain", 1.0) for a in actuators], biasprm=[a.get("biasprm", (0.0, 0.0, 0.0)) for a in actuators],
+            forcelimited=[a.get("forcelimited", 0) for a in actuators],
+            forcerange=[a.get("forcerange", (0.0, 0.0)) for a in actuators]))
     A["tendon_num"] = np.array([len(t["jnt"]) for t in tendons], np.int32)
     maxw = max([len(t["jnt"]) for t in tendons] + [1])
     tj = np.full((len(tendons), maxw), -1, np.int32)

@@ -12,13 +12,15 @@ Every descriptor field maps to the MjModel attribute of the same name, except:
     come from the geoms' contype / conaffinity / condim / friction / solref / solimp / solmix /
     margin / gap, the weld tree and `exclude_signature`, by mjcf.candidate_pairs;
   * actuator_trnid / actuator_gear: column 0 of MuJoCo's [nu, 2] / [nu, 6];
+  * actuator_kind / actuator_gain / actuator_biasprm (only for a model with a non-motor actuator): general
+    where the bias is affine, gainprm[0] != 1 or forcelimited; gainprm[0]; biasprm[0:3];
   * tendon_jnt / tendon_coef: the joint wraps (wrap_objid / wrap_prm) from tendon_adr;
   * tendon_solref / tendon_solimp: MuJoCo's tendon_solref_lim / tendon_solimp_lim;
   * options: opt.timestep / gravity / impratio / tolerance / ls_tolerance / iterations /
     ls_iterations / solver / integrator, eulerdamp = not (opt.disableflags & mjDSBL_EULERDAMP),
     meaninertia = stat.meaninertia; the invweight0 arrays are MuJoCo's own (mj_setConst).
-Anything outside the kernels' feature set (ball / slide joints, non-motor actuators, non-touch
-sensors, elliptic cones, equality constraints, other geom types, ...) raises MJCFError, as the MJCF
+Anything outside the kernels' feature set (ball / slide joints, actuators with dynamics, affine gains or
+non-joint transmissions, non-touch sensors, elliptic cones, equality constraints, other geom types, ...) raises MJCFError, as the MJCF
 compiler does.
 """
 from __future__ import annotations
@@ -150,18 +152,36 @@ def compile_mjmodel(mj, mujoco=None) -> CompiledModel:
     A["site_type"] = np.array([smap.get(int(t), -1) for t in stype], np.int32)
     A["site_bodyid"] = a("site_bodyid", np.int32)
     A["site_pos"], A["site_quat"], A["site_size"] = a("site_pos"), a("site_quat"), a("site_size")
-    # ---- actuators: motors on hinge joints (gain 1, no bias, no dynamics)
+    # ---- actuators on hinge joints: motors (gain 1, no bias, no force limit) and stateless general actuators
+    # (fixed gain, affine bias, force range); a model of motors alone carries the arrays it always did
+    general = None
     if nu:
-        if np.any(a("actuator_trntype", np.int32) != E("mjtTrn", "mjTRN_JOINT")) \
-                or np.any(a("actuator_dyntype", np.int32) != E("mjtDyn", "mjDYN_NONE")) \
-                or np.any(a("actuator_gaintype", np.int32) != E("mjtGain", "mjGAIN_FIXED")) \
-                or np.any(a("actuator_biastype", np.int32) != E("mjtBias", "mjBIAS_NONE")) \
-                or np.any(a("actuator_gainprm").reshape(nu, -1)[:, 0] != 1.0):
-            raise MJCFError("only motor actuators (joint transmission) supported")
+        if np.any(a("actuator_trntype", np.int32) != E("mjtTrn", "mjTRN_JOINT")):
+            raise MJCFError("only joint transmission supported (actuator_trntype)")
+        if np.any(a("actuator_dyntype", np.int32) != E("mjtDyn", "mjDYN_NONE")):
+            raise MJCFError("actuator activation state not supported (actuator_dyntype other than none)")
+        if np.any(a("actuator_gaintype", np.int32) != E("mjtGain", "mjGAIN_FIXED")):
+            raise MJCFError("only fixed actuator gains supported (actuator_gaintype)")
+        biastype = a("actuator_biastype", np.int32)
+        affine = biastype != E("mjtBias", "mjBIAS_NONE")
+        if np.any(affine) and np.any(biastype[affine] != E("mjtBias", "mjBIAS_AFFINE")):
+            raise MJCFError("only affine actuator biases supported (actuator_biastype muscle / user)")
+        gain = a("actuator_gainprm").reshape(nu, -1)[:, 0].copy()
+        flim = np.array(getattr(mj, "actuator_forcelimited", np.zeros(nu)), np.int32).reshape(nu)
+        is_general = affine | (gain != 1.0) | (flim != 0)
+        if np.any(is_general):
+            bias = np.zeros((nu, 3))
+            if np.any(affine):
+                bias[affine] = a("actuator_biasprm").reshape(nu, -1)[affine, :3]
+            frange = a("actuator_forcerange").reshape(nu, 2) if np.any(flim) else np.zeros((nu, 2))
+            general = mjcf.general_actuator_arrays(np.where(is_general, mjcf.ACT_GENERAL, mjcf.ACT_MOTOR), gain, bias,
+                                                   flim, frange)
     A["actuator_trnid"] = a("actuator_trnid", np.int32).reshape(nu, 2)[:, 0].copy()
     A["actuator_gear"] = a("actuator_gear").reshape(nu, 6)[:, 0].copy()
     A["actuator_ctrlrange"] = a("actuator_ctrlrange").reshape(nu, 2)
     A["actuator_ctrllimited"] = a("actuator_ctrllimited", np.int32)
+    if general is not None:
+        A.update(general)
     # ---- fixed tendons over joints
     tadr, tnum = a("tendon_adr", np.int32), a("tendon_num", np.int32)
     maxw = max([int(n) for n in tnum] + [1])

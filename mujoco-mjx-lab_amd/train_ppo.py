@@ -48,7 +48,15 @@ def parse_args(argv=None):
         ap.add_argument(f"--rand-{name}", type=float, nargs=2, metavar=("LO", "HI"), default=None,
                         help=f"domain randomisation of the training envs: {what}, uniform in [LO, HI] times the "
                              "model's value, drawn once at start (off by default)")
+    ap.add_argument("--pd-control", type=float, nargs=2, metavar=("KP", "KV"), default=None,
+                    help="joint-target actions: the motors become PD actuators (stiffness KP, damping KV) that hold "
+                         "qpos0 + S * action within the motors' torque limits, in the training and evaluation envs "
+                         "(off by default)")
+    ap.add_argument("--action-scale", type=float, default=None, metavar="S",
+                    help="radians of joint target per unit action with --pd-control (default 1)")
     a = ap.parse_args(argv)
+    if a.action_scale is not None and a.pd_control is None:
+        ap.error("--action-scale needs --pd-control KP KV")
     if a.push_force is None and (a.push_interval or a.push_duration is not None or a.push_body):
         ap.error("--push-interval / --push-duration / --push-body need --push-force LO HI")
     return a
@@ -63,6 +71,15 @@ def push_config(a, model, env_cfg):
         raise SystemExit(f"--push-body: no body named {a.push_body!r}")
     return {"body": body, "interval": tuple(a.push_interval or (100, 200)),
             "duration": 5 if a.push_duration is None else a.push_duration, "force": tuple(a.push_force)}
+
+
+def control_model(a, model):
+    """The model the envs run: `model` itself without --pd-control (nothing new is built or launched), else its
+    copy with PD actuators (mjx_amd.actuators.pd_actuators)."""
+    if a.pd_control is None:
+        return model
+    from mjx_amd.actuators import pd_actuators
+    return pd_actuators(model, a.pd_control[0], a.pd_control[1], 1.0 if a.action_scale is None else a.action_scale)
 
 
 def randomize_config(a):
@@ -96,7 +113,7 @@ def main():
     if world > 1:
         import torch.distributed as dist
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    model = mjx_amd.load_model(a.model or os.path.splitext(os.path.basename(cfg.xml_path))[0])
+    model = control_model(a, mjx_amd.load_model(a.model or os.path.splitext(os.path.basename(cfg.xml_path))[0]))
     sys_ = mjx.put_model(model)
     env_cfg = resolve_ids(model, cfg.env_config)
     env = HumanoidEnv(sys_, env_cfg, cfg.num_envs // world, device=local, seed=cfg.seed * 7919 + rank)

@@ -12,6 +12,14 @@
 // body_rootmass, any_damping and both homes of the damping follow the substituted values, and that nothing
 // outside the substituted fields' homes differs from the unsubstituted block. One line per file:
 //   <file>\tparams=ok|FAILED: <what>
+//
+//   model_host_check --block DESC_FILE...
+// Writes the model block (the raw bytes of ModelF) that model_build makes of each descriptor to <file>.block.
+// One line per file:
+//   <file>\trc=<code>\tsizeof_ModelF=<bytes>\tmotor_bytes=<offset of ModelF::arec>\tact_general=<0|1>\tact_b2=<0|1>
+// Descriptors with general actuators (MJL_ACT_GENERAL) go through every mode like any other: gear has one home
+// in the block (the flat actuator_gear), so --params' byte comparison also shows that a substituted gear leaves
+// nothing derived behind in the general actuators' records.
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -107,6 +115,35 @@ int main(int argc, char** argv) {
       std::printf("%s\tparams=%s%s\n", argv[a], why.empty() ? "ok" : "FAILED: ", why.c_str());
     }
     return bad ? 1 : 0;
+  }
+  if (argc > 1 && std::strcmp(argv[1], "--block") == 0) {
+    for (int a = 2; a < argc; a++) {
+      std::unique_ptr<mjlModelDesc> d(new mjlModelDesc);
+      std::unique_ptr<mjl::ModelF> f(new mjl::ModelF);
+      FILE* fp = std::fopen(argv[a], "rb");
+      const bool whole = fp && std::fread(d.get(), sizeof(mjlModelDesc), 1, fp) == 1 && std::fgetc(fp) == EOF;
+      if (fp) std::fclose(fp);
+      if (!whole) {
+        std::fprintf(stderr, "%s: not a file of %zu bytes (one mjlModelDesc)\n", argv[a], sizeof(mjlModelDesc));
+        return 2;
+      }
+      int nefc_max = 0, ncon_max = 0;
+      std::string msg;
+      const int rc = mjl::model_build(d.get(), *f, nefc_max, ncon_max, msg);
+      if (rc == MJL_OK) {
+        const std::string out = std::string(argv[a]) + ".block";
+        FILE* fo = std::fopen(out.c_str(), "wb");
+        const bool ok = fo && std::fwrite(f.get(), sizeof(mjl::ModelF), 1, fo) == 1;
+        if (fo) std::fclose(fo);
+        if (!ok) {
+          std::fprintf(stderr, "%s: cannot write\n", out.c_str());
+          return 2;
+        }
+      }
+      std::printf("%s\trc=%d\tsizeof_ModelF=%zu\tmotor_bytes=%zu\tact_general=%d\tact_b2=%d\n", argv[a], rc,
+                  sizeof(mjl::ModelF), offsetof(mjl::ModelF, arec), rc ? 0 : f->act_general, rc ? 0 : f->act_b2);
+    }
+    return 0;
   }
   for (int a = 1; a < argc; a++) {
     // on the heap, exactly sized: the sanitizer sees any read or write past either struct
