@@ -44,6 +44,8 @@ extern "C" {
 #define MJL_MAXTENWRAP 4
 #define MJL_MAXPAIR 256
 #define MJL_MAXSENSOR 4
+#define MJL_MAXRSENSOR 128
+#define MJL_MAXRSENSORDATA 256
 #define MJL_MAXOBS 64
 
 /* enums (MuJoCo numbering where one exists) */
@@ -53,7 +55,18 @@ enum { MJL_SOLVER_CG = 1, MJL_SOLVER_NEWTON = 2 };
 enum { MJL_INT_EULER = 0, MJL_INT_IMPLICITFAST = 3 };
 enum { MJL_COL_PLANE_SPHERE = 0, MJL_COL_PLANE_CAPSULE = 1, MJL_COL_SPHERE_SPHERE = 2,
        MJL_COL_SPHERE_CAPSULE = 3, MJL_COL_CAPSULE_CAPSULE = 4 };
-enum { MJL_SENS_TOUCH = 0 };
+/* Sensor types and object types of the readout table (mjlModelDesc.rsensor_*, mjl_sensors). The numbering is
+ * this project's own, not MuJoCo's mjtSensor / mjtObj; MJL_SENS_TOUCH stays 0. Stage of each type
+ * (mj_sensorPos / mj_sensorVel / mj_sensorAcc): pos = JOINTPOS, FRAMEPOS, FRAMEQUAT, FRAME[XYZ]AXIS; vel =
+ * JOINTVEL, GYRO, VELOCIMETER, FRAMELINVEL, FRAMEANGVEL; acc = TOUCH, ACCELEROMETER, ACTUATORFRC,
+ * JOINTACTUATORFRC, JOINTLIMITFRC. MJL_OBJ_TOUCH: the object is an entry of the touch list (sensor_*). */
+enum { MJL_SENS_TOUCH = 0, MJL_SENS_JOINTPOS = 1, MJL_SENS_JOINTVEL = 2, MJL_SENS_FRAMEPOS = 3,
+       MJL_SENS_FRAMEQUAT = 4, MJL_SENS_FRAMEXAXIS = 5, MJL_SENS_FRAMEYAXIS = 6, MJL_SENS_FRAMEZAXIS = 7,
+       MJL_SENS_GYRO = 8, MJL_SENS_VELOCIMETER = 9, MJL_SENS_FRAMELINVEL = 10, MJL_SENS_FRAMEANGVEL = 11,
+       MJL_SENS_ACCELEROMETER = 12, MJL_SENS_ACTUATORFRC = 13, MJL_SENS_JOINTACTUATORFRC = 14,
+       MJL_SENS_JOINTLIMITFRC = 15, MJL_NSENSTYPE = 16 };
+enum { MJL_OBJ_XBODY = 0, MJL_OBJ_SITE = 1, MJL_OBJ_JOINT = 2, MJL_OBJ_ACTUATOR = 3, MJL_OBJ_TOUCH = 4 };
+enum { MJL_SENS_STAGE_POS = 1, MJL_SENS_STAGE_VEL = 2, MJL_SENS_STAGE_ACC = 4 };
 enum { MJL_ACT_MOTOR = 0, MJL_ACT_GENERAL = 1 };
 
 typedef struct mjlModelDesc {
@@ -108,6 +121,16 @@ typedef struct mjlModelDesc {
   double tendon_margin[MJL_MAXTENDON], tendon_solref[MJL_MAXTENDON][2];
   double tendon_solimp[MJL_MAXTENDON][5], tendon_invweight0[MJL_MAXTENDON];
 
+  /* Readout table (mjl_sensors): ALL sensors in declaration order, MuJoCo's sensor ids, so adr / dim are the
+   * layout of Data.sensordata [nrsensordata]. type: MJL_SENS_*; objtype: MJL_OBJ_*; objid: a body (XBODY), site,
+   * joint (a hinge) or actuator id, or, for a touch sensor, its index in the touch list below; dim: 1, 3 or 4 by
+   * type. Slices [adr, adr + dim) lie inside [0, nrsensordata) and do not overlap. nrsensor = 0: no readout. */
+  int32_t nrsensor, nrsensordata;
+  int32_t rsensor_type[MJL_MAXRSENSOR], rsensor_objtype[MJL_MAXRSENSOR], rsensor_objid[MJL_MAXRSENSOR];
+  int32_t rsensor_adr[MJL_MAXRSENSOR], rsensor_dim[MJL_MAXRSENSOR];
+
+  /* The touch list: the touch sensors the step kernels run (nsensor <= MJL_MAXSENSOR entries, nsensordata their
+   * width, MJL_FIELD_SENSORDATA their values; the env config's touch ids index it). It closes the struct. */
   int32_t sensor_type[MJL_MAXSENSOR], sensor_objid[MJL_MAXSENSOR], sensor_adr[MJL_MAXSENSOR];
 } mjlModelDesc;
 
@@ -267,6 +290,30 @@ int mjl_forward(mjlBatch* batch, const float* mask, void* stream);
 int mjl_forward_contacts(mjlBatch* batch, const float* mask, int max_con, int32_t* ncon, int32_t* geom,
                          int32_t* dim, int32_t* efc_adr, float* dist, float* pos, float* frame, float* force,
                          float* body_force, void* stream);
+
+/* Sensor readout: Data.sensordata of the batch's current state, every sensor of the model's readout table
+ * (mjlModelDesc.rsensor_*) as MuJoCo defines it (mj_sensorPos / mj_sensorVel / mj_sensorAcc; MJX sensor.py for
+ * the types it has). out: float [nenv, nrsensordata], sensor s of env e at out[e, adr[s] : adr[s] + dim[s]].
+ * With R, p the rotation and origin of the sensor's frame (an xbody: xpos / xquat; a site), w the angular
+ * velocity of the carrying body, p', p'' the classical world-frame velocity and acceleration of the point p:
+ *   pos  JOINTPOS qpos[jnt_qposadr]; FRAMEPOS p; FRAMEQUAT the unit quaternion of R; FRAME[XYZ]AXIS R's columns
+ *   vel  JOINTVEL qvel[jnt_dofadr]; GYRO R' w; VELOCIMETER R' p'; FRAMELINVEL p'; FRAMEANGVEL w
+ *   acc  TOUCH as MJL_FIELD_SENSORDATA; ACCELEROMETER R' (p'' - gravity) with Data.qacc; ACTUATORFRC the
+ *        actuator's scalar force after the force-range clamp; JOINTACTUATORFRC qfrc_actuator[dof];
+ *        JOINTLIMITFRC efc_force of the joint's limit row, 0 while the limit is inactive
+ * stages: a mask of MJL_SENS_STAGE_*; slots of sensors whose stage is not in it keep their content. Envs with
+ * mask <= 0.5 keep their rows (mask NULL = all envs).
+ * With MJL_SENS_STAGE_ACC the call first runs mjl_forward on the masked envs (applied forces and per-env model
+ * parameters take part as they do there, and the derived fields are left as that forward leaves them), so
+ * POS | VEL | ACC is mjx.forward(d).sensordata of the current state. Without it the call is one launch that
+ * reads qpos / qvel and the model only and writes nothing but out: the call to make after mjl_env_step for
+ * observations of the post-step state. ACTUATORFRC reads the env's own model block while
+ * MJL_OPT_PER_ENV_MODEL is on (the gear enters the force).
+ * No allocation, no synchronisation, capturable. MJL_ERR_ARG: null batch / out, stages 0 or with unknown bits.
+ * A model without readout sensors returns MJL_OK and launches nothing.
+ * mjl_model_nrsensordata: the row width (-1 for a null model). */
+int mjl_model_nrsensordata(const mjlModel* model);
+int mjl_sensors(mjlBatch* batch, const float* mask, int stages, float* out, void* stream);
 
 /* Replaces mjx.step (src/envs.py:345): ctrl (device [nenv, nu], may be NULL = keep current)
  * -> forward + integrate, state updated in place. */

@@ -20,6 +20,7 @@
 #include "twin_kernels.hip"
 #include "render_kernels.hip"
 #include "contact_kernels.hip"
+#include "sensor_kernels.hip"
 #include "model_host.h"
 
 using namespace mjl;
@@ -50,6 +51,7 @@ int fail(int code, const char* fmt, ...) {
 struct mjlModel {
   mjlModelDesc desc;
   ModelF mf;
+  SensorTab st;  // the readout table of mjl_sensors (st.n = 0: the model has none)
   int nefc_max, ncon_max, nvc;  // nvc: 0 = DHum kernels, 1 = DGen kernels
 };
 
@@ -108,6 +110,7 @@ struct mjlBatch {
   const float* xfrc_applied;
   ModelF* d_model_env;      // MJL_OPT_PER_ENV_MODEL: one model block per env, or null
   ParamStage* d_param_stage;  // what model_params_kernel needs beside the blocks (allocated with them)
+  SensorTab* d_sensors;       // the readout table beside the model block, or null (a model without readout sensors)
 };
 
 // one launch of the per-env block builder: `fill` copies the shared block into every env's
@@ -147,6 +150,7 @@ int mjl_model_create(const mjlModelDesc* d, mjlModel** out) {
   std::string msg;
   if (int rc = model_build(d, M->mf, M->nefc_max, M->ncon_max, msg)) return fail(rc, "%s", msg.c_str());
   M->desc = *d;
+  sensor_tab_build(d, M->st);
   // compact kernel instantiation when the model fits the humanoid capacities, generic otherwise
   M->nvc = (d->nv <= DHum::NV && d->nbody <= DHum::NB && d->njnt <= DHum::NJ && d->ngeom <= DHum::NG) ? 0 : 1;
   *out = M.release();
@@ -156,6 +160,7 @@ int mjl_model_create(const mjlModelDesc* d, mjlModel** out) {
 void mjl_model_destroy(mjlModel* m) { delete m; }
 int mjl_model_nefc_max(const mjlModel* m) { return m ? m->nefc_max : -1; }
 int mjl_model_ncon_max(const mjlModel* m) { return m ? m->ncon_max : -1; }
+int mjl_model_nrsensordata(const mjlModel* m) { return m ? m->st.ndata : -1; }
 
 int mjl_batch_create(const mjlModel* model, int nenv, int device, mjlBatch** out) {
   if (!model || !out || nenv <= 0) return fail(MJL_ERR_ARG, "bad argument");
@@ -201,6 +206,10 @@ int mjl_batch_create(const mjlModel* model, int nenv, int device, mjlBatch** out
   if (e == hipSuccess) e = hipMalloc(&B->d_model, sizeof(ModelF));
   if (e == hipSuccess) e = hipMemcpy(B->d_model, &model->mf, sizeof(ModelF), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc(&B->d_env, sizeof(mjlEnvConfig));
+  if (e == hipSuccess && model->st.n > 0) {
+    e = hipMalloc(&B->d_sensors, sizeof(SensorTab));
+    if (e == hipSuccess) e = hipMemcpy(B->d_sensors, &model->st, sizeof(SensorTab), hipMemcpyHostToDevice);
+  }
   // global overflow rows for envs whose active constraints exceed the LDS capacity
   int LD = model->nvc == 0 ? DHum::LD : DGen::LD;
   B->gmax_efc = model->nefc_max > 0 ? model->nefc_max : 1;
@@ -210,6 +219,7 @@ int mjl_batch_create(const mjlModel* model, int nenv, int device, mjlBatch** out
   if (e == hipSuccess) e = hipMalloc(&B->d_scratch, (size_t)B->scratch_stride * nenv * sizeof(float));
   if (e != hipSuccess) {
     (void)hipFree(B->d_state); (void)hipFree(B->d_model); (void)hipFree(B->d_env); (void)hipFree(B->d_scratch);
+    (void)hipFree(B->d_sensors);
     delete B;
     return fail(MJL_ERR_HIP, "batch allocation: %s", hipGetErrorString(e));
   }
@@ -226,6 +236,7 @@ void mjl_batch_destroy(mjlBatch* B) {
   (void)hipFree(B->d_exp_stage);
   (void)hipFree(B->d_rs); (void)hipFree(B->d_pool_ctl); (void)hipFree(B->d_vtape);
   (void)hipFree(B->d_model_env); (void)hipFree(B->d_param_stage);
+  (void)hipFree(B->d_sensors);
   delete B;
 }
 
@@ -541,6 +552,33 @@ int mjl_forward_contacts(mjlBatch* B, const float* mask, int max_con, int32_t* n
     hipLaunchKernelGGL(contacts_kernel<DGen>, grid, block, 0, (hipStream_t)stream, (const ModelF*)B->d_model,
                        (const float*)B->s.stats, mask, B->d_scratch, B->scratch_stride, B->gmax_efc, B->gmax_con,
                        B->nenv, O);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
+}
+
+// With the acc stage two launches, as mjl_forward_contacts: the forward pass with this call's rows in the global
+// slab, then the readout (sensor_kernels.hip), which reads the derived store and the limit rows. Without it
+// the readout alone, from qpos / qvel and the model.
+int mjl_sensors(mjlBatch* B, const float* mask, int stages, float* out, void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (!out) return fail(MJL_ERR_ARG, "out is required");
+  const int all = MJL_SENS_STAGE_POS | MJL_SENS_STAGE_VEL | MJL_SENS_STAGE_ACC;
+  if (stages == 0 || (stages & ~all)) return fail(MJL_ERR_ARG, "stages = %d: a nonzero mask of MJL_SENS_STAGE_*", stages);
+  if (!B->d_sensors) return MJL_OK;  // no readout sensors
+  if (stages & MJL_SENS_STAGE_ACC) {
+    KParams P = make_params(B);
+    P.mask = mask;
+    P.force_global_rows = 1;
+    if (int rc = launch<MODE_FORWARD, true>(B, P, stream)) return rc;
+  } else {
+    HIPCHK(hipSetDevice(B->device));
+  }
+  SensorArgs A;
+  A.m = B->d_model; A.m_env = B->d_model_env; A.tab = B->d_sensors; A.s = B->s; A.mask = mask;
+  A.scratch = B->d_scratch; A.scratch_stride = B->scratch_stride; A.gmax_efc = B->gmax_efc; A.gmax_con = B->gmax_con;
+  A.LD = B->model->nvc == 0 ? DHum::LD : DGen::LD;
+  A.nenv = B->nenv; A.stages = stages; A.out = out;
+  hipLaunchKernelGGL(sensors_kernel, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
   HIPCHK(hipGetLastError());
   return MJL_OK;
 }

@@ -28,6 +28,8 @@ struct alignas(16) HingeRec {
 };
 // geom (index < 32) / site (index 32 + s) frame constants, by lane: body, local pos, local z axis
 // (geoms, mat[0..2]) or local rotation (sites)
+constexpr int kSiteLane = 32;  // ModelF::frec[kSiteLane + s] is site s; the geoms take the lanes below it
+static_assert(MJL_MAXGEOM <= kSiteLane && kSiteLane + MJL_MAXSITE <= 64, "geom and site frames share one 64-lane table");
 struct alignas(16) FrameRec {
   int body, pad0, pad1, pad2;
   float pos[3], pad3;
@@ -154,6 +156,26 @@ struct ModelF {
 // DESIGN.md ("Per-env model parameters"): a change of ModelF changes those figures with this one.
 static_assert(offsetof(ModelF, arec) == 45936, "the motor-only part of the block keeps its layout");
 static_assert(sizeof(ModelF) == 46976, "sizeof(ModelF) is documented: update the figures named above");
+
+// The readout table of mjl_sensors (sensor_kernels.hip): a small block of its own beside the model block, so
+// ModelF and the per-env model blocks keep their size. Built by sensor_tab_build (model_host.h).
+struct SensorTab {
+  int n, ndata, stages, pad;  // stages: the MJL_SENS_STAGE_* bits some entry has
+  int type[MJL_MAXRSENSOR], objtype[MJL_MAXRSENSOR], objid[MJL_MAXRSENSOR];
+  int adr[MJL_MAXRSENSOR], dim[MJL_MAXRSENSOR], stage[MJL_MAXRSENSOR];
+  float site_quat[MJL_MAXSITE][4];
+};
+// dim and stage of a sensor type (MJL_SENS_*)
+constexpr int sensor_type_dim(int type) {
+  return type == MJL_SENS_FRAMEQUAT ? 4
+         : (type == MJL_SENS_TOUCH || type == MJL_SENS_JOINTPOS || type == MJL_SENS_JOINTVEL ||
+            type >= MJL_SENS_ACTUATORFRC) ? 1 : 3;
+}
+constexpr int sensor_type_stage(int type) {
+  return (type == MJL_SENS_TOUCH || type >= MJL_SENS_ACCELEROMETER) ? MJL_SENS_STAGE_ACC
+         : (type == MJL_SENS_JOINTVEL || (type >= MJL_SENS_GYRO && type <= MJL_SENS_FRAMEANGVEL)) ? MJL_SENS_STAGE_VEL
+         : MJL_SENS_STAGE_POS;
+}
 
 // MODE_APPLIED: a flag on MODE_FORWARD / MODE_STEP / MODE_ENV_STEP in step_kernel's template argument, the
 // instantiations that read the applied forces (KParams::qfrc_applied / xfrc_applied)

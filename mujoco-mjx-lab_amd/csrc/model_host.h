@@ -136,8 +136,60 @@ inline int model_check(const mjlModelDesc* d, std::string& msg) {
     MJL_RANGE("sensor_objid", s, d->sensor_objid[s], 0, d->nsite);  // touch sensors: a site
     MJL_RANGE("sensor_adr", s, d->sensor_adr[s], 0, d->nsensordata);
   }
+  // the readout table (mjl_sensors): every entry's type, object and slice of the sensordata row
+  if (d->nrsensor < 0 || d->nrsensordata < 0)
+    return model_err(msg, MJL_ERR_ARG, "nrsensor = %d / nrsensordata = %d is negative", d->nrsensor, d->nrsensordata);
+  if (d->nrsensor > MJL_MAXRSENSOR || d->nrsensordata > MJL_MAXRSENSORDATA)
+    return model_err(msg, MJL_ERR_UNSUPPORTED, "readout table exceeds its capacities (%d sensors, %d values)",
+                     MJL_MAXRSENSOR, MJL_MAXRSENSORDATA);
+  bool used[MJL_MAXRSENSORDATA] = {};
+  for (int s = 0; s < d->nrsensor; s++) {
+    const int type = d->rsensor_type[s], ot = d->rsensor_objtype[s], id = d->rsensor_objid[s];
+    if (type < 0 || type >= MJL_NSENSTYPE)
+      return model_err(msg, MJL_ERR_UNSUPPORTED, "rsensor_type[%d] = %d not supported", s, type);
+    const int dim = sensor_type_dim(type);
+    bool ok_obj;
+    switch (type) {
+      case MJL_SENS_TOUCH: ok_obj = ot == MJL_OBJ_TOUCH; break;
+      case MJL_SENS_JOINTPOS: case MJL_SENS_JOINTVEL: case MJL_SENS_JOINTACTUATORFRC: case MJL_SENS_JOINTLIMITFRC:
+        ok_obj = ot == MJL_OBJ_JOINT; break;
+      case MJL_SENS_GYRO: case MJL_SENS_VELOCIMETER: case MJL_SENS_ACCELEROMETER: ok_obj = ot == MJL_OBJ_SITE; break;
+      case MJL_SENS_ACTUATORFRC: ok_obj = ot == MJL_OBJ_ACTUATOR; break;
+      default: ok_obj = ot == MJL_OBJ_XBODY || ot == MJL_OBJ_SITE; break;  // the frame sensors
+    }
+    if (!ok_obj)
+      return model_err(msg, MJL_ERR_UNSUPPORTED, "rsensor_objtype[%d] = %d not supported for sensor type %d", s, ot, type);
+    const int nobj = ot == MJL_OBJ_XBODY ? d->nbody : ot == MJL_OBJ_SITE ? d->nsite : ot == MJL_OBJ_JOINT ? d->njnt
+                     : ot == MJL_OBJ_ACTUATOR ? d->nu : d->nsensor;
+    MJL_RANGE("rsensor_objid", s, id, 0, nobj);
+    if (ot == MJL_OBJ_JOINT && d->jnt_type[id] != MJL_JNT_HINGE)
+      return model_err(msg, MJL_ERR_UNSUPPORTED, "rsensor %d: a joint sensor on a free joint is not supported", s);
+    if (d->rsensor_dim[s] != dim)
+      return model_err(msg, MJL_ERR_ARG, "rsensor_dim[%d] = %d: sensor type %d has dim %d", s, d->rsensor_dim[s], type, dim);
+    MJL_RANGE("rsensor_adr", s, d->rsensor_adr[s], 0, d->nrsensordata - dim + 1);
+    for (int k = d->rsensor_adr[s]; k < d->rsensor_adr[s] + dim; k++) {
+      if (used[k]) return model_err(msg, MJL_ERR_ARG, "rsensor_adr[%d] = %d: the slice overlaps another sensor's", s, d->rsensor_adr[s]);
+      used[k] = true;
+    }
+  }
 #undef MJL_RANGE
   return MJL_OK;
+}
+
+// The readout table's device block (SensorTab, model_dev.h), beside the model block: the table as it stands in
+// the descriptor, the stage of each entry, and the site quaternions (ModelF keeps the sites' matrices only).
+// `d` has passed model_check.
+inline void sensor_tab_build(const mjlModelDesc* d, SensorTab& t) {
+  std::memset(&t, 0, sizeof(t));
+  t.n = d->nrsensor; t.ndata = d->nrsensordata;
+  for (int s = 0; s < d->nrsensor; s++) {
+    t.type[s] = d->rsensor_type[s]; t.objtype[s] = d->rsensor_objtype[s]; t.objid[s] = d->rsensor_objid[s];
+    t.adr[s] = d->rsensor_adr[s]; t.dim[s] = d->rsensor_dim[s];
+    t.stage[s] = sensor_type_stage(d->rsensor_type[s]);
+    t.stages |= t.stage[s];
+  }
+  for (int s = 0; s < d->nsite; s++)
+    for (int i = 0; i < 4; i++) t.site_quat[s][i] = (float)d->site_quat[s][i];
 }
 
 // Fills `f` (every byte) and the two capacities the row storage is sized with: the most constraint rows and
@@ -253,7 +305,7 @@ inline int model_build(const mjlModelDesc* d, ModelF& f, int& nefc_max, int& nco
     }
   }
   for (int s = 0; s < d->nsite; s++) {
-    FrameRec& r = f.frec[32 + s];
+    FrameRec& r = f.frec[kSiteLane + s];
     r.body = f.site_bodyid[s] = d->site_bodyid[s];
     double sm[9];
     q2m_host(d->site_quat[s], sm);

@@ -14,8 +14,9 @@ BUILTIN_MODELS = ("humanoid_mjx", "humanoid")
 
 
 def __getattr__(name):
-    # the contact readout of `mjx` (mjl_forward_contacts), resolved on first use: `mjx` imports torch
-    if name in ("Contacts", "forward_contacts"):
+    # the contact and sensor readouts of `mjx` (mjl_forward_contacts, mjl_sensors), resolved on first use:
+    # `mjx` imports torch
+    if name in ("Contacts", "forward_contacts", "sensors"):
         from . import mjx
         return getattr(mjx, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

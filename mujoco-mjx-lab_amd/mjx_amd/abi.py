@@ -57,7 +57,12 @@ RENDER_SHADOWS = _E["MJL_RENDER_SHADOWS"]
 _PY = {C.c_int32: int, C.c_float: float, C.c_double: float}  # what a scalar field is set through
 _CAP = {n: _D["MJL_MAX" + c] for n, c in (
     ("nbody", "BODY"), ("njnt", "JNT"), ("nv", "V"), ("nq", "Q"), ("ngeom", "GEOM"), ("npair", "PAIR"),
-    ("nsite", "SITE"), ("nu", "U"), ("ntendon", "TENDON"), ("nsensor", "SENSOR"))}
+    ("nsite", "SITE"), ("nu", "U"), ("ntendon", "TENDON"), ("nsensor", "SENSOR"),
+    ("nrsensor", "RSENSOR"), ("nrsensordata", "RSENSORDATA"))}
+# readout sensors (mjl_sensors): "gyro": MJL_SENS_GYRO, ...; "pos" / "vel" / "acc": MJL_SENS_STAGE_*
+SENSOR_TYPE = {k[9:].lower(): v for k, v in _E.items() if k.startswith("MJL_SENS_") and not k.startswith("MJL_SENS_STAGE_")}
+SENSOR_STAGE = {k[15:].lower(): v for k, v in _E.items() if k.startswith("MJL_SENS_STAGE_")}
+SENSOR_OBJ = {k[8:].lower(): v for k, v in _E.items() if k.startswith("MJL_OBJ_")}
 
 
 class UnsupportedModel(ValueError):

@@ -29,8 +29,13 @@ def resolve_ids(m, cfg: EnvConfig) -> EnvConfig:
     """Body / sensor id lookup done by reference load_model_and_create_env (training_utils.py:84-89)."""
     cfg.pelvis_body_id = m.name2id("body", "pelvis")
     cfg.head_body_id = m.name2id("body", "head")
-    cfg.touch_sensor_right_id = m.name2id("sensor", "touch_foot_right")
-    cfg.touch_sensor_left_id = m.name2id("sensor", "touch_foot_left")
+    def touch(name):  # the env's touch ids index the touch list, not the model's sensors (the readout table)
+        s = m.name2id("sensor", name)
+        if s < 0 or "rsensor_type" not in m.arrays:
+            return s
+        return int(m.arrays["rsensor_objid"][s]) if m.arrays["rsensor_type"][s] == 0 else -1
+    cfg.touch_sensor_right_id = touch("touch_foot_right")
+    cfg.touch_sensor_left_id = touch("touch_foot_left")
     if min(cfg.pelvis_body_id, cfg.head_body_id, cfg.touch_sensor_right_id, cfg.touch_sensor_left_id) < 0:
         raise MjlError("model lacks pelvis/head bodies or touch_foot_* sensors")
     return cfg
@@ -114,6 +119,13 @@ class HumanoidEnv:
 
     def get_model_params(self, name: str) -> torch.Tensor:
         return self.data.get_model_params(name)
+
+    def sensors(self, mask: Optional[torch.Tensor] = None, stages: Optional[int] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Data.sensordata [num_envs, sys.nrsensordata] of the envs' current state (mjx.sensors): after step(),
+        with stages = pos | vel, one launch on the post-step state, capturable with the step."""
+        from .mjx import sensors
+        return sensors(self.sys, self.data, mask, stages, out)
 
     def _next_counter(self) -> int:
         self.counter += 1

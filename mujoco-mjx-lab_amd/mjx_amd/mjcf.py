@@ -11,6 +11,9 @@ reference humanoid models use (`models/humanoid_mjx.xml`, `models/humanoid.xml`)
 * contype/conaffinity, parent filtering, `<contact><exclude>`, contact-parameter mixing
 * limited hinges (degrees -> radians), armature/damping/stiffness, fixed tendons with limits
 * motors (joint transmission, gear, ctrlrange), touch sensors on box sites, keyframes
+* the readout sensors of mjl_sensors (SENSOR_TYPES: IMU, joint, frame and force sensors on hinges, sites, xbodies
+  and actuators), all sensors in declaration order in the rsensor_* arrays; other elements, objtype body / geom,
+  reftype, a nonzero cutoff and joint sensors on a free joint are refused with the sensor's name
 * <position kp kv inheritrange>, <velocity kv>, <general gaintype="fixed" biastype="none|affine"> on hinges
   (gear, ctrlrange, forcerange, class and per-tag <default>s); dampratio, timeconst, dyntype, other gain /
   bias types and non-joint transmissions are refused by name
@@ -35,7 +38,37 @@ GEOM_PLANE, GEOM_HFIELD, GEOM_SPHERE, GEOM_CAPSULE, GEOM_ELLIPSOID, GEOM_CYLINDE
 JNT_FREE, JNT_BALL, JNT_SLIDE, JNT_HINGE = 0, 1, 2, 3
 SOLVER_PGS, SOLVER_CG, SOLVER_NEWTON = 0, 1, 2
 INT_EULER, INT_RK4, INT_IMPLICIT, INT_IMPLICITFAST = 0, 1, 2, 3
-SENS_TOUCH = 0  # our own numbering (only touch is supported)
+# Sensor types, object types and stages: our own numbering (include/mjx355.h MJL_SENS_* / MJL_OBJ_* /
+# MJL_SENS_STAGE_*, which tests/test_sensors.py compares with these), not MuJoCo's mjtSensor / mjtObj
+SENS_TOUCH = 0
+SENSOR_TYPES = {"touch": 0, "jointpos": 1, "jointvel": 2, "framepos": 3, "framequat": 4, "framexaxis": 5,
+                "frameyaxis": 6, "framezaxis": 7, "gyro": 8, "velocimeter": 9, "framelinvel": 10, "frameangvel": 11,
+                "accelerometer": 12, "actuatorfrc": 13, "jointactuatorfrc": 14, "jointlimitfrc": 15}
+OBJ_XBODY, OBJ_SITE, OBJ_JOINT, OBJ_ACTUATOR, OBJ_TOUCH = 0, 1, 2, 3, 4
+STAGE_POS, STAGE_VEL, STAGE_ACC = 1, 2, 4
+MAXRSENSOR, MAXRSENSORDATA = 128, 256
+READOUT_ARRAYS = ("rsensor_type", "rsensor_objtype", "rsensor_objid", "rsensor_adr", "rsensor_dim")
+_SENSOR_OBJ = {"touch": "site", "gyro": "site", "velocimeter": "site", "accelerometer": "site",
+               "jointpos": "joint", "jointvel": "joint", "jointactuatorfrc": "joint", "jointlimitfrc": "joint",
+               "actuatorfrc": "actuator"}  # the frame sensors take objtype / objname
+
+
+def sensor_dim(type_: int) -> int:
+    return 4 if type_ == SENSOR_TYPES["framequat"] else 1 if type_ in (0, 1, 2, 13, 14, 15) else 3
+
+
+def sensor_stage(type_: int) -> int:
+    return STAGE_ACC if type_ == 0 or type_ >= 12 else STAGE_VEL if type_ == 2 or 8 <= type_ <= 11 else STAGE_POS
+
+
+def readout_arrays(rsensors) -> Dict[str, np.ndarray]:
+    """The readout table's five arrays from a list of {type, objtype, objid, adr, dim}."""
+    return {"rsensor_" + k: np.array([s[k] for s in rsensors], np.int32) for k in ("type", "objtype", "objid", "adr", "dim")}
+
+
+def touch_readout(nsensor: int):
+    """The readout entries of a touch-only model: sensor s is entry s of the touch list, at adr s."""
+    return [{"type": SENS_TOUCH, "objtype": OBJ_TOUCH, "objid": s, "adr": s, "dim": 1} for s in range(nsensor)]
 
 # collision kinds (our numbering; geom1 type <= geom2 type as MuJoCo dispatches them)
 COL_PLANE_SPHERE, COL_PLANE_CAPSULE, COL_SPHERE_SPHERE, COL_SPHERE_CAPSULE, COL_CAPSULE_CAPSULE = 0, 1, 2, 3, 4
@@ -176,6 +209,23 @@ class CompiledModel:
     def qpos0(self) -> np.ndarray:
         return self.arrays["qpos0"]
 
+    # the readout table (rsensor_* arrays): every sensor in declaration order, the layout of Data.sensordata
+    @property
+    def nrsensor(self) -> int:
+        return len(self.arrays.get("rsensor_type", ()))
+
+    @property
+    def nrsensordata(self) -> int:
+        return int(np.sum(self.arrays["rsensor_dim"])) if self.nrsensor else 0
+
+    def sensor_slice(self, name: str) -> slice:
+        """Where sensor `name` lies in a sensordata row of mjx.sensors."""
+        s = self.name2id("sensor", name)
+        if s < 0 or not name:
+            raise KeyError(f"no sensor named '{name}'")
+        adr = int(self.arrays["rsensor_adr"][s])
+        return slice(adr, adr + int(self.arrays["rsensor_dim"][s]))
+
     def to_json_dict(self) -> dict:
         d = {k: getattr(self, k) for k in (
             "name", "source_sha256", "nq", "nv", "nu", "nbody", "njnt", "ngeom", "nsite", "ntendon",
@@ -198,6 +248,8 @@ class CompiledModel:
                 m.gravity = np.array(v, float)
             else:
                 setattr(m, k, v)
+        if "sensor_type" in m.arrays and "rsensor_type" not in m.arrays:  # written before the readout table:
+            m.arrays.update(readout_arrays(touch_readout(len(m.arrays["sensor_type"]))))  # a touch-only model
         return m
 
 
@@ -315,6 +367,38 @@ def _general_actuator(a_el, defaults: "_Defaults", jnt_names, joints) -> dict:
     fr = _floats(a["forcerange"]) if "forcerange" in a else [0.0, 0.0]
     return {"jnt": jid, "gear": _floats(a["gear"])[0], "ctrlrange": cr, "ctrllimited": limited, "gain": gain,
             "biasprm": bias, "forcelimited": _auto_limited(a, "forcelimited", "forcerange", tag), "forcerange": fr}
+
+
+def _readout_sensor(s_el, defaults: "_Defaults", names, sites, joints) -> dict:
+    """One <sensor> child as a readout entry {type, objtype, objid, dim} (adr is set by the caller; a touch
+    sensor's objid is its site here). Everything outside the supported set raises with the sensor's name."""
+    tag = s_el.tag
+    a = defaults.resolve(tag, s_el, None)
+    label = f"sensor <{tag}>" + (f" '{a['name']}'" if a.get("name") else "")
+    if tag not in SENSOR_TYPES:
+        raise MJCFError(f"{label} not supported")
+    if "reftype" in a or "refname" in a:
+        raise MJCFError(f"{label}: reftype / refname not supported")
+    if float(a.get("cutoff", "0")) != 0:
+        raise MJCFError(f"{label}: a nonzero cutoff is not supported")
+    # `noise` is accepted and ignored, as MuJoCo's simulation ignores it
+    if tag in _SENSOR_OBJ:
+        kind, oname = _SENSOR_OBJ[tag], a.get(_SENSOR_OBJ[tag])
+    else:
+        kind, oname = a.get("objtype"), a.get("objname")
+        if kind not in ("xbody", "site"):
+            raise MJCFError(f"{label}: objtype='{kind}' not supported (xbody, site)")
+    if oname is None or oname not in names[kind]:
+        raise MJCFError(f"{label}: unknown {kind} '{oname}'")
+    oid = names[kind].index(oname)
+    if kind == "joint" and joints[oid]["type"] != JNT_HINGE:
+        raise MJCFError(f"{label}: a joint sensor on a free joint is not supported")
+    if tag == "touch" and sites[oid]["type"] != GEOM_BOX:
+        raise MJCFError(f"{label}: touch sensor requires a box site")
+    t = SENSOR_TYPES[tag]
+    objtype = OBJ_TOUCH if tag == "touch" else {"xbody": OBJ_XBODY, "site": OBJ_SITE, "joint": OBJ_JOINT,
+                                               "actuator": OBJ_ACTUATOR}[kind]
+    return {"type": t, "objtype": objtype, "objid": oid, "dim": sensor_dim(t)}
 
 
 def _geom_inertia(gtype: int, size, density: float):
@@ -736,18 +820,24 @@ def compile_xml_string(text: str, name_hint: str = "", sha: str = "") -> Compile
             ten_names.append(t_el.get("name", ""))
 
     # ---- sensors -----------------------------------------------------------------------------
+    # `sensors`: the touch list the step kernels run; `rsensors`: every sensor in declaration order (MuJoCo's
+    # sensor ids), the readout table of mjl_sensors and the layout of Data.sensordata
     sen = root.find("sensor")
     sensors = []
+    rsensors = []
     sen_names = []
     if sen is not None:
         for s_el in sen:
-            if s_el.tag != "touch":
-                raise MJCFError(f"sensor <{s_el.tag}> not supported")
-            sid = site_names.index(s_el.get("site"))
-            if sites[sid]["type"] != GEOM_BOX:
-                raise MJCFError("touch sensor requires a box site")
-            sensors.append({"type": SENS_TOUCH, "objid": sid, "adr": len(sensors), "dim": 1})
+            r = _readout_sensor(s_el, defaults, {"site": site_names, "joint": jnt_names, "actuator": act_names,
+                                                 "xbody": body_names}, sites, joints)
+            if r["type"] == SENS_TOUCH:
+                r["objid"], site = len(sensors), r["objid"]
+                sensors.append({"type": SENS_TOUCH, "objid": site, "adr": len(sensors), "dim": 1})
+            r["adr"] = sum(x["dim"] for x in rsensors)
+            rsensors.append(r)
             sen_names.append(s_el.get("name", ""))
+        if len(rsensors) > MAXRSENSOR or sum(x["dim"] for x in rsensors) > MAXRSENSORDATA:
+            raise MJCFError(f"more than {MAXRSENSOR} sensors or {MAXRSENSORDATA} sensor values not supported")
 
     # ---- keyframes ---------------------------------------------------------------------------
     keys, key_names = [], []
@@ -858,6 +948,7 @@ def compile_xml_string(text: str, name_hint: str = "", sha: str = "") -> Compile
     A["sensor_type"] = np.array([s["type"] for s in sensors], np.int32)
     A["sensor_objid"] = np.array([s["objid"] for s in sensors], np.int32)
     A["sensor_adr"] = np.array([s["adr"] for s in sensors], np.int32)
+    A.update(readout_arrays(rsensors))
     A["key_qpos"] = np.array(keys).reshape(-1, nq)
     A["exclude_signature"] = np.array(sorted((b1 << 16) + b2 for b1, b2 in excludes), np.int64)  # MjModel's
 

@@ -16,11 +16,14 @@ Every descriptor field maps to the MjModel attribute of the same name, except:
     where the bias is affine, gainprm[0] != 1 or forcelimited; gainprm[0]; biasprm[0:3];
   * tendon_jnt / tendon_coef: the joint wraps (wrap_objid / wrap_prm) from tendon_adr;
   * tendon_solref / tendon_solimp: MuJoCo's tendon_solref_lim / tendon_solimp_lim;
+  * sensor_* : the touch sensors alone (the touch list the step kernels run); rsensor_*: every sensor in
+    MuJoCo's id order with MuJoCo's sensor_adr / sensor_dim, type and object codes translated by name to this
+    project's (mjcf.SENSOR_TYPES, OBJ_*), a touch sensor's objid its index in the touch list;
   * options: opt.timestep / gravity / impratio / tolerance / ls_tolerance / iterations /
     ls_iterations / solver / integrator, eulerdamp = not (opt.disableflags & mjDSBL_EULERDAMP),
     meaninertia = stat.meaninertia; the invweight0 arrays are MuJoCo's own (mj_setConst).
 Anything outside the kernels' feature set (ball / slide joints, actuators with dynamics, affine gains or
-non-joint transmissions, non-touch sensors, elliptic cones, equality constraints, other geom types, ...) raises MJCFError, as the MJCF
+non-joint transmissions, sensors outside mjcf.SENSOR_TYPES, elliptic cones, equality constraints, other geom types, ...) raises MJCFError, as the MJCF
 compiler does.
 """
 from __future__ import annotations
@@ -42,6 +45,36 @@ def _enum(mujoco, enum_name: str, member: str) -> int:
 def _name(mujoco, mj, obj: str, i: int) -> str:
     n = mujoco.mj_id2name(mj, _enum(mujoco, "mjtObj", obj), i)
     return n or ""
+
+
+def _readout_from_mjmodel(mj, mujoco, st, objid, touch_ids, jnt_type):
+    """The readout table of an MjModel with non-touch sensors: MuJoCo's sensor / object type codes (read from the
+    bindings by name) to this project's, MuJoCo's sensor_adr / sensor_dim kept; what mjcf refuses is refused."""
+    code = {int(getattr(mujoco.mjtSensor, "mjSENS_" + k.upper())): v for k, v in mjcf.SENSOR_TYPES.items()}
+    obj = {int(getattr(mujoco.mjtObj, "mjOBJ_" + k)): v for k, v in (
+        ("XBODY", mjcf.OBJ_XBODY), ("SITE", mjcf.OBJ_SITE), ("JOINT", mjcf.OBJ_JOINT), ("ACTUATOR", mjcf.OBJ_ACTUATOR))}
+    adr, dim = np.array(mj.sensor_adr, np.int32), np.array(mj.sensor_dim, np.int32)
+    ot, rt = np.array(mj.sensor_objtype, np.int32), np.array(mj.sensor_reftype, np.int32)
+    cutoff = np.array(mj.sensor_cutoff, np.float64)
+    rs = []
+    for s in range(len(st)):
+        name = _name(mujoco, mj, "mjOBJ_SENSOR", s) or str(s)
+        if int(st[s]) not in code:
+            raise MJCFError(f"sensor '{name}': type {int(st[s])} not supported")
+        t = code[int(st[s])]
+        if cutoff[s] != 0 or int(rt[s]) != int(mujoco.mjtObj.mjOBJ_UNKNOWN):
+            raise MJCFError(f"sensor '{name}': cutoff / reftype not supported")
+        if t == mjcf.SENS_TOUCH:
+            rs.append({"type": t, "objtype": mjcf.OBJ_TOUCH, "objid": touch_ids.index(s), "adr": int(adr[s]), "dim": 1})
+            continue
+        if int(ot[s]) not in obj:
+            raise MJCFError(f"sensor '{name}': object type {int(ot[s])} not supported (xbody, site, joint, actuator)")
+        if obj[int(ot[s])] == mjcf.OBJ_JOINT and jnt_type[objid[s]] != mjcf.JNT_HINGE:
+            raise MJCFError(f"sensor '{name}': a joint sensor on a free joint is not supported")
+        if int(dim[s]) != mjcf.sensor_dim(t):
+            raise MJCFError(f"sensor '{name}': dim {int(dim[s])}")
+        rs.append({"type": t, "objtype": obj[int(ot[s])], "objid": int(objid[s]), "adr": int(adr[s]), "dim": int(dim[s])})
+    return rs
 
 
 def compile_mjmodel(mj, mujoco=None) -> CompiledModel:
@@ -203,23 +236,34 @@ def compile_mjmodel(mj, mujoco=None) -> CompiledModel:
     A["tendon_solref"] = a("tendon_solref_lim").reshape(ntendon, 2)
     A["tendon_solimp"] = a("tendon_solimp_lim").reshape(ntendon, 5)
     A["tendon_invweight0"] = a("tendon_invweight0")
-    # ---- touch sensors on box sites
+    # ---- sensors: the touch list (touch sensors on box sites, what the step kernels run) and the readout table
+    # (every sensor in MuJoCo's id order with MuJoCo's sensor_adr / sensor_dim: the Data.sensordata layout)
     st = a("sensor_type", np.int32)
-    if np.any(st != E("mjtSensor", "mjSENS_TOUCH")):
-        raise MJCFError("only touch sensors supported")
-    A["sensor_type"] = np.full(nsensor, mjcf.SENS_TOUCH, np.int32)
-    A["sensor_objid"], A["sensor_adr"] = a("sensor_objid", np.int32), a("sensor_adr", np.int32)
+    touch_code = E("mjtSensor", "mjSENS_TOUCH")
+    touch_ids = [s for s in range(nsensor) if st[s] == touch_code]
+    mj_objid = a("sensor_objid", np.int32)
+    A["sensor_type"] = np.full(len(touch_ids), mjcf.SENS_TOUCH, np.int32)
+    A["sensor_objid"] = np.array([mj_objid[s] for s in touch_ids], np.int32)
+    A["sensor_adr"] = np.arange(len(touch_ids), dtype=np.int32)
     if any(A["site_type"][s] != mjcf.GEOM_BOX for s in A["sensor_objid"]):
         raise MJCFError("touch sensor requires a box site")
+    if len(touch_ids) == nsensor:
+        rs = mjcf.touch_readout(nsensor)
+        for s, r in enumerate(rs):
+            r["adr"] = int(a("sensor_adr", np.int32)[s])
+    else:
+        rs = _readout_from_mjmodel(mj, mujoco, st, mj_objid, touch_ids, A["jnt_type"])
+    A.update(mjcf.readout_arrays(rs))
+    nsensor = len(touch_ids)  # below, as in the MJCF compiler: the touch list's length
     A["key_qpos"] = a("key_qpos").reshape(-1, nq)
 
     m.arrays = A
     m.names = {kind: [_name(mujoco, mj, obj, i) for i in range(n)] for kind, obj, n in (
         ("body", "mjOBJ_BODY", nbody), ("joint", "mjOBJ_JOINT", njnt), ("geom", "mjOBJ_GEOM", ngeom),
         ("site", "mjOBJ_SITE", nsite), ("actuator", "mjOBJ_ACTUATOR", nu), ("tendon", "mjOBJ_TENDON", ntendon),
-        ("sensor", "mjOBJ_SENSOR", nsensor), ("key", "mjOBJ_KEY", int(mj.nkey)))}
+        ("sensor", "mjOBJ_SENSOR", int(mj.nsensor)), ("key", "mjOBJ_KEY", int(mj.nkey)))}
     m.nq, m.nv, m.nu = nq, nv, nu
     m.nbody, m.njnt, m.ngeom, m.nsite = nbody, njnt, ngeom, nsite
     m.ntendon, m.npair, m.nsensor = ntendon, len(pairs), nsensor
-    m.nsensordata, m.nkey = int(mj.nsensordata), int(mj.nkey)
+    m.nsensordata, m.nkey = nsensor, int(mj.nkey)  # the touch list's width; the readout's is m.nrsensordata
     return m

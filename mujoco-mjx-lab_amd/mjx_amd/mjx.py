@@ -61,6 +61,15 @@ class Model:
         """Most contacts one env can have: one per candidate pair, two per plane-capsule pair."""
         return lib().mjl_model_ncon_max(self._h)
 
+    @property
+    def nrsensordata(self) -> int:
+        """Width of a sensordata row of `sensors` (every sensor of the model, MuJoCo's Data.sensordata layout)."""
+        return lib().mjl_model_nrsensordata(self._h)
+
+    def sensor_slice(self, name: str) -> slice:
+        """Where sensor `name` lies in a row of `sensors`."""
+        return self.m.sensor_slice(name)
+
     def __del__(self):
         try:
             if getattr(self, "_h", None):
@@ -262,6 +271,26 @@ def forward_contacts(sys: Model, d: Data, mask: Optional[torch.Tensor] = None, m
                                      _iptr(c.efc_address), _ptr(c.dist), _ptr(c.pos), _ptr(c.frame), _ptr(c.force),
                                      _ptr(c.body_force), _stream()))
     return c
+
+
+def sensors(sys: Model, d: Data, mask: Optional[torch.Tensor] = None, stages: Optional[int] = None,
+            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Data.sensordata [nenv, sys.nrsensordata] of the current state: every sensor of the model (IMU, joint,
+    frame, force and touch sensors), sensor `name` at `sys.sensor_slice(name)`. stages: a mask of
+    abi.SENSOR_STAGE["pos" | "vel" | "acc"] (None: all three). With "acc" the call runs mjx.forward on the envs
+    with mask > 0.5 first, and the result is mjx.forward(d).sensordata; without it, it is one launch that reads
+    qpos / qvel only (observations after an env step, capturable). Slots of stages left out, and rows of envs
+    outside the mask, keep what `out` held (a fresh `out` is zeros). See include/mjx355.h mjl_sensors."""
+    st = sum(abi.SENSOR_STAGE.values()) if stages is None else int(stages)
+    n = sys.nrsensordata
+    if out is None:
+        out = torch.zeros((d.nenv, n), dtype=torch.float32, device=d.device)
+    elif tuple(out.shape) != (d.nenv, n) or out.device != d.device:
+        raise MjlError(f"out must have shape {(d.nenv, n)} on {d.device}")
+    mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
+    if n:  # (a model without sensors: nothing to launch, and an empty tensor has no address to pass)
+        check(lib().mjl_sensors(d.handle, _ptr(mk), st, _ptr(out), _stream()))
+    return out
 
 
 def step(sys: Model, d: Data, ctrl: Optional[torch.Tensor] = None) -> Data:

@@ -20,6 +20,12 @@
 // Descriptors with general actuators (MJL_ACT_GENERAL) go through every mode like any other: gear has one home
 // in the block (the flat actuator_gear), so --params' byte comparison also shows that a substituted gear leaves
 // nothing derived behind in the general actuators' records.
+//
+//   model_host_check --sensors DESC_FILE...
+// The readout table's device block (sensor_tab_build) of each accepted descriptor. One line per file:
+//   <file>\trc=0\tn=<sensors>\tndata=<values>\tstages=<mask>\tstage=<s0,s1,...>\tsite_quat0=<w,x,y,z of site 0>
+// The readout table's validation (types, object ids by object type, dims, slices) is part of model_build, so
+// the default mode covers its rejections (tests/test_sensors.py).
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -142,6 +148,32 @@ int main(int argc, char** argv) {
       }
       std::printf("%s\trc=%d\tsizeof_ModelF=%zu\tmotor_bytes=%zu\tact_general=%d\tact_b2=%d\n", argv[a], rc,
                   sizeof(mjl::ModelF), offsetof(mjl::ModelF, arec), rc ? 0 : f->act_general, rc ? 0 : f->act_b2);
+    }
+    return 0;
+  }
+  if (argc > 1 && std::strcmp(argv[1], "--sensors") == 0) {
+    for (int a = 2; a < argc; a++) {
+      std::unique_ptr<mjlModelDesc> d(new mjlModelDesc);
+      std::unique_ptr<mjl::ModelF> f(new mjl::ModelF);
+      std::unique_ptr<mjl::SensorTab> t(new mjl::SensorTab);
+      FILE* fp = std::fopen(argv[a], "rb");
+      const bool whole = fp && std::fread(d.get(), sizeof(mjlModelDesc), 1, fp) == 1 && std::fgetc(fp) == EOF;
+      if (fp) std::fclose(fp);
+      if (!whole) {
+        std::fprintf(stderr, "%s: not a file of %zu bytes (one mjlModelDesc)\n", argv[a], sizeof(mjlModelDesc));
+        return 2;
+      }
+      int nefc_max = 0, ncon_max = 0;
+      std::string msg;
+      const int rc = mjl::model_build(d.get(), *f, nefc_max, ncon_max, msg);
+      if (rc != MJL_OK) {
+        std::printf("%s\trc=%d\n", argv[a], rc);
+        continue;
+      }
+      mjl::sensor_tab_build(d.get(), *t);
+      std::printf("%s\trc=0\tn=%d\tndata=%d\tstages=%d\tstage=", argv[a], t->n, t->ndata, t->stages);
+      for (int s = 0; s < t->n; s++) std::printf("%s%d", s ? "," : "", t->stage[s]);
+      std::printf("\tsite_quat0=%g,%g,%g,%g\n", t->site_quat[0][0], t->site_quat[0][1], t->site_quat[0][2], t->site_quat[0][3]);
     }
     return 0;
   }
