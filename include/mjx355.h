@@ -219,9 +219,11 @@ int mjl_batch_nenv(const mjlBatch* batch);
  * mjl_env_fill_reset_pool fills (call outside stream capture; 0 frees it).
  * MJL_OPT_PER_ENV_MODEL (default 0): 1 gives every env a model block of its own, filled with the
  * model's values (nenv x 46976 bytes, the size of one device model block: 96 MB for 2048 envs; call
- * outside stream capture; 0 frees them). See mjl_batch_set_model_params. */
+ * outside stream capture; 0 frees them). See mjl_batch_set_model_params.
+ * MJL_OPT_RAY_CHUNK (default 0, tuning hook of tools/ray_bench.py): value = rays per wavefront of mjl_ray /
+ * mjl_ray_scan, 0..65535; 0 = the library's choice. The results do not depend on it. */
 enum { MJL_OPT_STORE_DERIVED = 0, MJL_OPT_FORCE_GLOBAL_ROWS = 1, MJL_OPT_VJP_UNROLLED = 2, MJL_OPT_RESET_POOL = 3,
-       MJL_OPT_VJP_TAPE = 4, MJL_OPT_PER_ENV_MODEL = 5 };
+       MJL_OPT_VJP_TAPE = 4, MJL_OPT_PER_ENV_MODEL = 5, MJL_OPT_RAY_CHUNK = 6 };
 int mjl_batch_set_option(mjlBatch* batch, int option, int value);
 
 /* Per-env model parameters (domain randomisation; in MJX jax.vmap(step, in_axes=(model_axes, 0)) over a
@@ -314,6 +316,42 @@ int mjl_forward_contacts(mjlBatch* batch, const float* mask, int max_con, int32_
  * mjl_model_nrsensordata: the row width (-1 for a null model). */
 int mjl_model_nrsensordata(const mjlModel* model);
 int mjl_sensors(mjlBatch* batch, const float* mask, int stages, float* out, void* stream);
+
+/* Ray casts against the batch's current state: mjx.ray / mj_ray (mjl_ray, caller-chosen world rays per env) and
+ * ray patterns carried by a body or site frame (mjl_ray_scan: height scanner, lidar fan, rangefinder).
+ * Buffers (float32 / int32, device): mjl_ray pnt, vec [nenv, nray, 3] in the world frame; mjl_ray_scan lpnt, lvec
+ * [nray, 3] in the frame; dist [nenv, nray]; geomid [nenv, nray] or NULL; hitpos [nenv, nray, 3] or NULL.
+ * Geometry: the geoms are posed by forward kinematics of the batch's current qpos, run in the same launch. No
+ * mjl_forward is needed first, the stored xpos / xquat are neither read nor written, so the call is correct
+ * right after mjl_env_step; it costs about what mjl_sensors with stages = pos costs. Per-env model parameters
+ * and applied forces do not matter (no geometric field is per-env).
+ * One ray: the smallest parameter t >= 0 with pnt + t vec on the surface of a geom that passes the filter, at
+ * most cutoff when cutoff > 0 (else unbounded). vec need not be unit length (t is found along vec / |vec| and
+ * scaled by 1 / |vec|; a zero vec misses); dist = t is in metres when it is. Per geom the renderer's closed
+ * forms: a plane's crossing; a sphere's or capsule's near crossing, or the far one when the near one lies behind
+ * the origin, so a ray that starts inside reports the exit point. geomid = the geom, ties going to the lower
+ * id. A miss: dist = -1, geomid = -1 (mj_ray's convention).
+ * Filter: geoms of body `bodyexclude` are skipped (-1: none); geoms of body 0 (the floor) are skipped unless
+ * flags has MJL_RAY_STATIC.
+ * mjl_ray_scan: the frame of objtype (MJL_OBJ_XBODY or MJL_OBJ_SITE) / objid, rotation R and origin p as the
+ * pos-stage sensors define them; lpnt / lvec [nray, 3] are shared by all envs.
+ *   MJL_SCAN_POSE  ray r is pnt = p + R lpnt[r], vec = R lvec[r]. A rangefinder is one ray with lpnt = 0,
+ *                  lvec = +z on a site, bodyexclude = the site's body.
+ *   MJL_SCAN_YAW   R is replaced by the rotation about world z by psi = atan2(R[1][0], R[0][0]) (psi = 0 when
+ *                  R[0][0]^2 + R[1][0]^2 < 1e-12): a grid that turns with the heading but stays level.
+ * hitpos = pnt + dist * vec in the world, pnt on a miss.
+ * Envs with mask <= 0.5 keep their output rows (mask NULL = all envs). All pointers are device pointers read at
+ * execution time. One launch, no allocation, no synchronisation, capturable.
+ * MJL_ERR_ARG: a null batch, dist, pnt, vec, lpnt or lvec; nray outside 1..65535; unknown flag bits or align;
+ * objtype other than the two above or objid out of range; bodyexclude outside -1..nbody-1.
+ * MJL_ERR_UNSUPPORTED: a model with a geom that is no plane, sphere or capsule (the renderer's rule). */
+enum { MJL_RAY_STATIC = 1 };
+enum { MJL_SCAN_POSE = 0, MJL_SCAN_YAW = 1 };
+int mjl_ray(mjlBatch* batch, const float* mask, int nray, const float* pnt, const float* vec, int flags,
+            int bodyexclude, float cutoff, float* dist, int32_t* geomid, void* stream);
+int mjl_ray_scan(mjlBatch* batch, const float* mask, int objtype, int objid, int align, int nray, const float* lpnt,
+                 const float* lvec, int flags, int bodyexclude, float cutoff, float* dist, int32_t* geomid,
+                 float* hitpos, void* stream);
 
 /* Replaces mjx.step (src/envs.py:345): ctrl (device [nenv, nu], may be NULL = keep current)
  * -> forward + integrate, state updated in place. */

@@ -21,6 +21,7 @@
 #include "render_kernels.hip"
 #include "contact_kernels.hip"
 #include "sensor_kernels.hip"
+#include "ray_kernels.hip"
 #include "model_host.h"
 
 using namespace mjl;
@@ -111,6 +112,7 @@ struct mjlBatch {
   ModelF* d_model_env;      // MJL_OPT_PER_ENV_MODEL: one model block per env, or null
   ParamStage* d_param_stage;  // what model_params_kernel needs beside the blocks (allocated with them)
   SensorTab* d_sensors;       // the readout table beside the model block, or null (a model without readout sensors)
+  int ray_chunk;              // MJL_OPT_RAY_CHUNK: rays per wavefront of mjl_ray / mjl_ray_scan, 0 = kRayChunk
 };
 
 // one launch of the per-env block builder: `fill` copies the shared block into every env's
@@ -314,6 +316,11 @@ int mjl_batch_set_option(mjlBatch* B, int option, int value) {
       B->d_model_env = nullptr; B->d_param_stage = nullptr;
       return e != hipSuccess ? fail(MJL_ERR_HIP, "per-env model blocks (%zu bytes): %s", bytes, hipGetErrorString(e)) : rc;
     }
+    return MJL_OK;
+  }
+  if (option == MJL_OPT_RAY_CHUNK) {
+    if (value < 0 || value > 65535) return fail(MJL_ERR_ARG, "ray chunk: 0..65535 rays per wavefront");
+    B->ray_chunk = value;
     return MJL_OK;
   }
   return fail(MJL_ERR_ARG, "unknown option %d", option);
@@ -581,6 +588,66 @@ int mjl_sensors(mjlBatch* B, const float* mask, int stages, float* out, void* st
   hipLaunchKernelGGL(sensors_kernel, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
   HIPCHK(hipGetLastError());
   return MJL_OK;
+}
+
+// Rays per wavefront of rays_kernel (ray_kernels.hip) unless MJL_OPT_RAY_CHUNK says otherwise: every chunk's
+// wavefront repeats the env's kinematics. DESIGN.md "Rays" has the measurement behind the value.
+constexpr int kRayChunk = 64;
+
+// the checks mjl_ray and mjl_ray_scan share, then the launch
+static int launch_rays(mjlBatch* B, RayArgs& A, void* stream) {
+  const mjlModelDesc& d = B->model->desc;
+  if (A.nray < 1 || A.nray > 65535) return fail(MJL_ERR_ARG, "nray = %d outside 1..65535", A.nray);
+  if (A.flags & ~MJL_RAY_STATIC) return fail(MJL_ERR_ARG, "flags = %d: unknown bits (MJL_RAY_STATIC)", A.flags);
+  if (A.bodyexclude < -1 || A.bodyexclude >= d.nbody)
+    return fail(MJL_ERR_ARG, "bodyexclude = %d outside -1..%d", A.bodyexclude, d.nbody - 1);
+  for (int g = 0; g < d.ngeom; g++)
+    if (d.geom_type[g] != MJL_GEOM_PLANE && d.geom_type[g] != MJL_GEOM_SPHERE && d.geom_type[g] != MJL_GEOM_CAPSULE)
+      return fail(MJL_ERR_UNSUPPORTED, "rays: geom %d has type %d (plane, sphere and capsule are tested)", g,
+                  d.geom_type[g]);
+  A.m = B->d_model; A.qpos = B->s.qpos; A.nenv = B->nenv;
+  A.chunk = B->ray_chunk > 0 ? B->ray_chunk : kRayChunk;
+  A.nchunk = (A.nray + A.chunk - 1) / A.chunk;
+  const long long blocks = (long long)B->nenv * A.nchunk;
+  if (blocks > 0x7fffffffLL) return fail(MJL_ERR_ARG, "rays: %d envs x %d ray chunks exceed one launch", B->nenv, A.nchunk);
+  HIPCHK(hipSetDevice(B->device));
+  hipLaunchKernelGGL(rays_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, A);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
+}
+
+int mjl_ray(mjlBatch* B, const float* mask, int nray, const float* pnt, const float* vec, int flags, int bodyexclude,
+            float cutoff, float* dist, int32_t* geomid, void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (!dist) return fail(MJL_ERR_ARG, "dist is required");
+  if (!pnt) return fail(MJL_ERR_ARG, "pnt is required");
+  if (!vec) return fail(MJL_ERR_ARG, "vec is required");
+  RayArgs A = {};
+  A.mask = mask; A.pnt = pnt; A.vec = vec; A.nray = nray; A.scan = 0;
+  A.flags = flags; A.bodyexclude = bodyexclude; A.cutoff = cutoff;
+  A.dist = dist; A.geomid = geomid; A.hitpos = nullptr;
+  return launch_rays(B, A, stream);
+}
+
+int mjl_ray_scan(mjlBatch* B, const float* mask, int objtype, int objid, int align, int nray, const float* lpnt,
+                 const float* lvec, int flags, int bodyexclude, float cutoff, float* dist, int32_t* geomid,
+                 float* hitpos, void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (!dist) return fail(MJL_ERR_ARG, "dist is required");
+  if (!lpnt) return fail(MJL_ERR_ARG, "lpnt is required");
+  if (!lvec) return fail(MJL_ERR_ARG, "lvec is required");
+  const mjlModelDesc& d = B->model->desc;
+  if (objtype != MJL_OBJ_XBODY && objtype != MJL_OBJ_SITE)
+    return fail(MJL_ERR_ARG, "objtype = %d: MJL_OBJ_XBODY or MJL_OBJ_SITE", objtype);
+  const int nobj = objtype == MJL_OBJ_XBODY ? d.nbody : d.nsite;
+  if (objid < 0 || objid >= nobj) return fail(MJL_ERR_ARG, "objid = %d outside 0..%d", objid, nobj - 1);
+  if (align != MJL_SCAN_POSE && align != MJL_SCAN_YAW) return fail(MJL_ERR_ARG, "align = %d: MJL_SCAN_POSE or MJL_SCAN_YAW", align);
+  RayArgs A = {};
+  A.mask = mask; A.pnt = lpnt; A.vec = lvec; A.nray = nray; A.scan = 1;
+  A.objtype = objtype; A.objid = objid; A.align = align;
+  A.flags = flags; A.bodyexclude = bodyexclude; A.cutoff = cutoff;
+  A.dist = dist; A.geomid = geomid; A.hitpos = hitpos;
+  return launch_rays(B, A, stream);
 }
 
 int mjl_step(mjlBatch* B, const float* ctrl, void* stream) {

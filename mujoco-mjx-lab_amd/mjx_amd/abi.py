@@ -63,6 +63,8 @@ _CAP = {n: _D["MJL_MAX" + c] for n, c in (
 SENSOR_TYPE = {k[9:].lower(): v for k, v in _E.items() if k.startswith("MJL_SENS_") and not k.startswith("MJL_SENS_STAGE_")}
 SENSOR_STAGE = {k[15:].lower(): v for k, v in _E.items() if k.startswith("MJL_SENS_STAGE_")}
 SENSOR_OBJ = {k[8:].lower(): v for k, v in _E.items() if k.startswith("MJL_OBJ_")}
+RAY_STATIC = _E["MJL_RAY_STATIC"]  # mjl_ray / mjl_ray_scan flags
+SCAN_ALIGN = {k[9:].lower(): v for k, v in _E.items() if k.startswith("MJL_SCAN_")}  # "pose", "yaw"
 
 
 class UnsupportedModel(ValueError):

@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import NamedTuple, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import abi
@@ -126,6 +127,26 @@ class HumanoidEnv:
         with stages = pos | vel, one launch on the post-step state, capturable with the step."""
         from .mjx import sensors
         return sensors(self.sys, self.data, mask, stages, out)
+
+    def scan(self, frame, pattern, align: str = "pose", flg_static: bool = True, bodyexclude="self",
+             cutoff: float = 0.0, mask: Optional[torch.Tensor] = None):
+        """Range scan of the envs' current state (mjx.ray_scan): `pattern` = (lpnt, lvec) [nray, 3] in the frame
+        of body / site `frame` (mjx_amd.rays.grid_pattern, fan_pattern) -> (dist, geomid, hitpos). The pattern's
+        device copy and the three outputs are allocated at the first call with this (frame, align, pattern) and
+        written again by every later one (the same tensors come back; rows of envs outside `mask` keep their
+        content, -1 / -1 / 0 at first), so after one eager call the scan is one launch on the post-step state
+        that can be captured with the step, as sensors()."""
+        from .mjx import ray_scan
+        lp, lv = (np.ascontiguousarray(np.asarray(x.cpu() if torch.is_tensor(x) else x, np.float32)) for x in pattern)
+        key = (str(frame), align, lp.tobytes(), lv.tobytes())
+        bufs = self.__dict__.setdefault("_scan_bufs", {})
+        if key not in bufs:
+            dev, n, r = self.obs.device, self.num_envs, lp.shape[0]
+            bufs[key] = (torch.tensor(lp, device=dev), torch.tensor(lv, device=dev),
+                         (torch.full((n, r), -1.0, device=dev), torch.full((n, r), -1, dtype=torch.int32, device=dev),
+                          torch.zeros((n, r, 3), device=dev)))
+        dlp, dlv, out = bufs[key]
+        return ray_scan(self.sys, self.data, frame, dlp, dlv, align, flg_static, bodyexclude, cutoff, mask, out)
 
     def _next_counter(self) -> int:
         self.counter += 1

@@ -293,6 +293,115 @@ def sensors(sys: Model, d: Data, mask: Optional[torch.Tensor] = None, stages: Op
     return out
 
 
+def _body_arg(sys: Model, body, carrying: int = -1) -> int:
+    """bodyexclude as the library takes it: an id (-1: none), a body name, or "self" (the carrying body)."""
+    if isinstance(body, str):
+        if body == "self":
+            if carrying < 0:
+                raise MjlError('bodyexclude="self" needs a carrying frame (ray_scan)')
+            return carrying
+        b = sys.m.name2id("body", body)
+        if b < 0:
+            raise MjlError(f"no body named {body!r}")
+        return b
+    return int(body)
+
+
+def _ray_out(d: Data, nray: int, out, masked: bool, hitpos: bool):
+    """(dist, geomid, hitpos) to write into: the caller's (entries None: not computed), or fresh ones holding
+    the miss values (what rows of envs outside the mask keep)."""
+    n, dev = d.nenv, d.device
+    if out is None:
+        mk = (lambda sh, dt, v: torch.full(sh, v, dtype=dt, device=dev)) if masked else \
+             (lambda sh, dt, v: torch.empty(sh, dtype=dt, device=dev))
+        out = (mk((n, nray), torch.float32, -1.0), mk((n, nray), torch.int32, -1),
+               mk((n, nray, 3), torch.float32, 0.0) if hitpos else None)
+    dist, geomid, hp = (tuple(out) + (None,))[:3]
+    if dist is None or tuple(dist.shape) != (n, nray):
+        raise MjlError(f"dist must have shape {(n, nray)}")
+    if geomid is not None and tuple(geomid.shape) != (n, nray):
+        raise MjlError(f"geomid must have shape {(n, nray)}")
+    if hp is not None and tuple(hp.shape) != (n, nray, 3):
+        raise MjlError(f"hitpos must have shape {(n, nray, 3)}")
+    return dist, geomid, hp
+
+
+def ray(sys: Model, d: Data, pnt, vec, flg_static: bool = True, bodyexclude=-1, cutoff: float = 0.0,
+        mask: Optional[torch.Tensor] = None, out=None):
+    """mjx.ray with a leading env axis: (dist, geomid) [nenv, nray] of rays pnt + t vec (world frame,
+    [nenv, nray, 3]; a [3] or [nray, 3] input is broadcast over the envs) against the geoms posed by the batch's
+    current qpos: no forward call is needed first. dist is the ray parameter of the nearest surface (metres for
+    a unit vec), -1 with geomid -1 for a miss; a ray starting inside a sphere or capsule reports the exit.
+    flg_static=False leaves out the geoms of the world body (the floor); bodyexclude (id, name, -1: none) the
+    geoms of one body; cutoff > 0 bounds t. Rows of envs with mask <= 0.5 keep what `out` held. out: (dist,
+    geomid) to write into, geomid may be None (then it is not computed and None is returned for it). One
+    launch, capturable when pnt / vec / out are device tensors of the full shape. See include/mjx355.h mjl_ray."""
+    def rays(x, what):
+        t = torch.as_tensor(x, dtype=torch.float32).to(d.device)
+        if t.dim() == 1:
+            t = t.view(1, 1, 3)
+        if t.dim() == 2:
+            t = t.unsqueeze(0)
+        if t.dim() != 3 or t.shape[-1] != 3:
+            raise MjlError(f"{what} must be [3], [nray, 3] or [nenv, nray, 3]")
+        return t
+    p, v = rays(pnt, "pnt"), rays(vec, "vec")
+    nray = max(p.shape[1], v.shape[1])
+    try:
+        p, v = (t.expand(d.nenv, nray, 3).contiguous() for t in (p, v))
+    except RuntimeError:
+        raise MjlError(f"pnt {tuple(p.shape)} and vec {tuple(v.shape)} do not broadcast to {(d.nenv, nray, 3)}") from None
+    dist, geomid, _ = _ray_out(d, nray, out, mask is not None, False)
+    mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
+    check(lib().mjl_ray(d.handle, _ptr(mk), nray, _ptr(p), _ptr(v), abi.RAY_STATIC if flg_static else 0,
+                        _body_arg(sys, bodyexclude), float(cutoff), _ptr(dist),
+                        None if geomid is None else _iptr(geomid), _stream()))
+    return dist, geomid
+
+
+def scan_frame(sys: Model, frame):
+    """(objtype, objid, carrying body) of a scan frame: a body or site name (bodies first), or an
+    ("xbody" | "site", id) pair."""
+    m = sys.m
+    if isinstance(frame, str):
+        kind = "xbody" if m.name2id("body", frame) >= 0 else "site"
+        i = m.name2id("body" if kind == "xbody" else "site", frame)
+        if i < 0:
+            raise MjlError(f"no body or site named {frame!r}")
+    else:
+        kind, i = frame[0], int(frame[1])
+        if kind not in ("xbody", "site"):
+            raise MjlError('frame must be a name or an ("xbody" | "site", id) pair')
+    if kind == "xbody":
+        return abi.SENSOR_OBJ["xbody"], i, i
+    body = int(m.arrays["site_bodyid"][i]) if 0 <= i < m.nsite else -1
+    return abi.SENSOR_OBJ["site"], i, body
+
+
+def ray_scan(sys: Model, d: Data, frame, lpnt, lvec, align: str = "pose", flg_static: bool = True, bodyexclude=-1,
+             cutoff: float = 0.0, mask: Optional[torch.Tensor] = None, out=None):
+    """A ray pattern carried by a body or site frame (height scanner, lidar fan, rangefinder): (dist, geomid,
+    hitpos), [nenv, nray], [nenv, nray] and [nenv, nray, 3] (world). lpnt / lvec [nray, 3] are in the frame and
+    shared by the envs (mjx_amd.rays has patterns). align="pose": ray r is p + R lpnt[r], R lvec[r] with the
+    frame's rotation R and origin p; align="yaw": R is the rotation about world z by the frame's heading, so a
+    grid turns with the body but stays level. bodyexclude="self" leaves out the carrying body's geoms; the
+    other arguments are `ray`'s. out: (dist, geomid, hitpos) to write into, the last two may be None. One
+    launch, capturable when lpnt / lvec / out are device tensors. See include/mjx355.h mjl_ray_scan."""
+    if align not in abi.SCAN_ALIGN:
+        raise MjlError(f"align must be one of {sorted(abi.SCAN_ALIGN)}")
+    objtype, objid, body = scan_frame(sys, frame)
+    lp, lv = (torch.as_tensor(x, dtype=torch.float32).to(d.device).contiguous() for x in (lpnt, lvec))
+    if lp.dim() != 2 or lp.shape[1] != 3 or lp.shape != lv.shape:
+        raise MjlError("lpnt and lvec must both be [nray, 3]")
+    nray = lp.shape[0]
+    dist, geomid, hitpos = _ray_out(d, nray, out, mask is not None, True)
+    mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
+    check(lib().mjl_ray_scan(d.handle, _ptr(mk), objtype, objid, abi.SCAN_ALIGN[align], nray, _ptr(lp), _ptr(lv),
+                             abi.RAY_STATIC if flg_static else 0, _body_arg(sys, bodyexclude, body), float(cutoff),
+                             _ptr(dist), None if geomid is None else _iptr(geomid), _ptr(hitpos), _stream()))
+    return dist, geomid, hitpos
+
+
 def step(sys: Model, d: Data, ctrl: Optional[torch.Tensor] = None) -> Data:
     if ctrl is not None:
         ctrl = ctrl.to(device=d.device, dtype=torch.float32).contiguous()
