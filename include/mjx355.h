@@ -317,6 +317,47 @@ int mjl_forward_contacts(mjlBatch* batch, const float* mask, int max_con, int32_
 int mjl_model_nrsensordata(const mjlModel* model);
 int mjl_sensors(mjlBatch* batch, const float* mask, int stages, float* out, void* stream);
 
+/* Body-level Data readout of the batch's current state: mjx.Data's xipos, ximat, subtree_com, cinert, cvel,
+ * subtree_linvel, subtree_angmom, cfrc_ext and cfrc_int. Every output is float32 on the device, [nenv, nbody, k]
+ * with k = 3, 9, 3, 10, 6, 3, 3, 6, 6 in the order of the arguments; an output passed as NULL is not wanted and
+ * costs nothing. All quantities are in the world frame. With b a body, k ranging over subtree(b) = [b,
+ * body_subtree_end[b]), c0 = subtree_com[body_rootid[b]], R_k / x_k the body frame, w_k / dw_k its angular velocity
+ * and acceleration, v_k / a_k the classical velocity and acceleration of the body's centre of mass xipos_k, T_k the
+ * body-frame tensor body_inertia, I_k = R_k T_k R_k' (= ximat_k diag(principal moments) ximat_k') and g gravity:
+ *   pos  xipos           xpos + xmat body_ipos
+ *        ximat           xmat quat2mat(body_iquat), row-major; body_iquat: the principal axes of T_b, the moments
+ *                        in descending order, a proper rotation (moments that coincide leave the axes within their
+ *                        eigenspace to the library: the body axes where T_b is diagonal). Row 0: the identity
+ *        subtree_com[b]  sum_k m_k xipos_k / sum_k m_k; row 0 is the whole model; a massless subtree gives xipos_b
+ *        cinert[b]       MuJoCo's 10-vector: [0..5] the rotational inertia about c0 in the order (xx, yy, zz, xy,
+ *                        xz, yz), I_b + m_b (|r|^2 1 - r r') with r = xipos_b - c0; [6..8] m_b r; [9] m_b
+ *   vel  cvel[b]         [w_b ; velocity of the body-fixed point at c0]: MuJoCo's com-based spatial velocity
+ *        subtree_linvel[b]  sum_k m_k v_k / sum_k m_k (0 for a massless subtree)
+ *        subtree_angmom[b]  sum_k [ I_k w_k + m_k (xipos_k - subtree_com_b) x (v_k - subtree_linvel_b) ]: the
+ *                        angular momentum about the subtree's own centre of mass
+ *   acc  cfrc_ext[b]     [torque about c0 ; force] of the external loads on body b alone: its attached xfrc_applied
+ *                        row (the force at xipos_b, plus its torque) and every contact force of the forward pass,
+ *                        acting at the contact's pos: + frame' force on geom2's body and the opposite on geom1's
+ *                        (mjl_forward_contacts' convention); a contact with the world loads the moving side only
+ *        cfrc_int[b]     sum_k { [ I_k dw_k + w_k x I_k w_k + (xipos_k - c0) x m_k (a_k - g) ; m_k (a_k - g) ]
+ *                        - cfrc_ext[k] }: the wrench the parent exerts on b through their joint, about c0, what
+ *                        mj_rnePostConstraint accumulates (MuJoCo's force / torque sensors). A free root's is 0
+ *                        up to the solver's residual (qfrc_applied, a generalized force, is not a body load)
+ * Row 0 (the world) of cinert, cvel, cfrc_ext and cfrc_int is zero.
+ * Envs with mask <= 0.5 keep their rows (mask NULL = all envs).
+ * With neither cfrc output the call is one launch that reads qpos / qvel and the model only and writes nothing but
+ * the outputs: the call to make after mjl_env_step. With one, the call first runs mjl_forward on the masked envs
+ * (applied forces and per-env model parameters take part as they do there, and the derived fields are left as that
+ * forward leaves them), then reads its qacc and contacts.
+ * While MJL_OPT_PER_ENV_MODEL is on, body_mass, body_inertia (T_k) and body_ipos are the env's own block's;
+ * body_iquat stays the model's (a per-env tensor enters I_k in full, whatever its axes).
+ * No allocation, no synchronisation, capturable. MJL_ERR_ARG: null batch, or all nine outputs NULL. */
+int mjl_body_data(mjlBatch* batch, const float* mask,
+                  float* xipos, float* ximat, float* subtree_com, float* cinert,      /* pos */
+                  float* cvel, float* subtree_linvel, float* subtree_angmom,           /* vel */
+                  float* cfrc_ext, float* cfrc_int,                                    /* acc */
+                  void* stream);
+
 /* Ray casts against the batch's current state: mjx.ray / mj_ray (mjl_ray, caller-chosen world rays per env) and
  * ray patterns carried by a body or site frame (mjl_ray_scan: height scanner, lidar fan, rangefinder).
  * Buffers (float32 / int32, device): mjl_ray pnt, vec [nenv, nray, 3] in the world frame; mjl_ray_scan lpnt, lvec

@@ -21,6 +21,7 @@
 #include "render_kernels.hip"
 #include "contact_kernels.hip"
 #include "sensor_kernels.hip"
+#include "body_kernels.hip"
 #include "ray_kernels.hip"
 #include "model_host.h"
 
@@ -53,6 +54,7 @@ struct mjlModel {
   mjlModelDesc desc;
   ModelF mf;
   SensorTab st;  // the readout table of mjl_sensors (st.n = 0: the model has none)
+  BodyTab bt;    // body_iquat, for mjl_body_data's ximat
   int nefc_max, ncon_max, nvc;  // nvc: 0 = DHum kernels, 1 = DGen kernels
 };
 
@@ -112,6 +114,7 @@ struct mjlBatch {
   ModelF* d_model_env;      // MJL_OPT_PER_ENV_MODEL: one model block per env, or null
   ParamStage* d_param_stage;  // what model_params_kernel needs beside the blocks (allocated with them)
   SensorTab* d_sensors;       // the readout table beside the model block, or null (a model without readout sensors)
+  BodyTab* d_bodytab;         // body_iquat beside the model block (mjl_body_data)
   int ray_chunk;              // MJL_OPT_RAY_CHUNK: rays per wavefront of mjl_ray / mjl_ray_scan, 0 = kRayChunk
 };
 
@@ -153,6 +156,7 @@ int mjl_model_create(const mjlModelDesc* d, mjlModel** out) {
   if (int rc = model_build(d, M->mf, M->nefc_max, M->ncon_max, msg)) return fail(rc, "%s", msg.c_str());
   M->desc = *d;
   sensor_tab_build(d, M->st);
+  body_tab_build(d, M->bt);
   // compact kernel instantiation when the model fits the humanoid capacities, generic otherwise
   M->nvc = (d->nv <= DHum::NV && d->nbody <= DHum::NB && d->njnt <= DHum::NJ && d->ngeom <= DHum::NG) ? 0 : 1;
   *out = M.release();
@@ -212,6 +216,8 @@ int mjl_batch_create(const mjlModel* model, int nenv, int device, mjlBatch** out
     e = hipMalloc(&B->d_sensors, sizeof(SensorTab));
     if (e == hipSuccess) e = hipMemcpy(B->d_sensors, &model->st, sizeof(SensorTab), hipMemcpyHostToDevice);
   }
+  if (e == hipSuccess) e = hipMalloc(&B->d_bodytab, sizeof(BodyTab));
+  if (e == hipSuccess) e = hipMemcpy(B->d_bodytab, &model->bt, sizeof(BodyTab), hipMemcpyHostToDevice);
   // global overflow rows for envs whose active constraints exceed the LDS capacity
   int LD = model->nvc == 0 ? DHum::LD : DGen::LD;
   B->gmax_efc = model->nefc_max > 0 ? model->nefc_max : 1;
@@ -221,7 +227,7 @@ int mjl_batch_create(const mjlModel* model, int nenv, int device, mjlBatch** out
   if (e == hipSuccess) e = hipMalloc(&B->d_scratch, (size_t)B->scratch_stride * nenv * sizeof(float));
   if (e != hipSuccess) {
     (void)hipFree(B->d_state); (void)hipFree(B->d_model); (void)hipFree(B->d_env); (void)hipFree(B->d_scratch);
-    (void)hipFree(B->d_sensors);
+    (void)hipFree(B->d_sensors); (void)hipFree(B->d_bodytab);
     delete B;
     return fail(MJL_ERR_HIP, "batch allocation: %s", hipGetErrorString(e));
   }
@@ -238,7 +244,7 @@ void mjl_batch_destroy(mjlBatch* B) {
   (void)hipFree(B->d_exp_stage);
   (void)hipFree(B->d_rs); (void)hipFree(B->d_pool_ctl); (void)hipFree(B->d_vtape);
   (void)hipFree(B->d_model_env); (void)hipFree(B->d_param_stage);
-  (void)hipFree(B->d_sensors);
+  (void)hipFree(B->d_sensors); (void)hipFree(B->d_bodytab);
   delete B;
 }
 
@@ -586,6 +592,39 @@ int mjl_sensors(mjlBatch* B, const float* mask, int stages, float* out, void* st
   A.LD = B->model->nvc == 0 ? DHum::LD : DGen::LD;
   A.nenv = B->nenv; A.stages = stages; A.out = out;
   hipLaunchKernelGGL(sensors_kernel, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
+}
+
+// With a cfrc output two launches, as mjl_sensors with its acc stage: the forward pass with this call's rows in
+// the global slab, then the readout (body_kernels.hip), which reads qacc, the contact count and the slab's
+// contacts. Without one the readout alone, from qpos / qvel and the model.
+int mjl_body_data(mjlBatch* B, const float* mask, float* xipos, float* ximat, float* subtree_com, float* cinert,
+                  float* cvel, float* subtree_linvel, float* subtree_angmom, float* cfrc_ext, float* cfrc_int,
+                  void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (!xipos && !ximat && !subtree_com && !cinert && !cvel && !subtree_linvel && !subtree_angmom && !cfrc_ext &&
+      !cfrc_int)
+    return fail(MJL_ERR_ARG, "mjl_body_data: every output is NULL");
+  if (cfrc_ext || cfrc_int) {
+    KParams P = make_params(B);
+    P.mask = mask;
+    P.force_global_rows = 1;
+    if (int rc = launch<MODE_FORWARD, true>(B, P, stream)) return rc;
+  } else {
+    HIPCHK(hipSetDevice(B->device));
+  }
+  BodyArgs A;
+  A.m = B->d_model; A.m_env = B->d_model_env; A.tab = B->d_bodytab; A.s = B->s; A.mask = mask;
+  A.xfrc = B->xfrc_applied;
+  A.scratch = B->d_scratch; A.scratch_stride = B->scratch_stride; A.gmax_efc = B->gmax_efc; A.gmax_con = B->gmax_con;
+  A.nenv = B->nenv;
+  A.xipos = xipos; A.ximat = ximat; A.subtree_com = subtree_com; A.cinert = cinert; A.cvel = cvel;
+  A.subtree_linvel = subtree_linvel; A.subtree_angmom = subtree_angmom; A.cfrc_ext = cfrc_ext; A.cfrc_int = cfrc_int;
+  if (B->model->nvc == 0)
+    hipLaunchKernelGGL(body_data_kernel<DHum>, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
+  else
+    hipLaunchKernelGGL(body_data_kernel<DGen>, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
   HIPCHK(hipGetLastError());
   return MJL_OK;
 }

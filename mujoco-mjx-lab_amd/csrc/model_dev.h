@@ -165,6 +165,12 @@ struct SensorTab {
   int adr[MJL_MAXRSENSOR], dim[MJL_MAXRSENSOR], stage[MJL_MAXRSENSOR];
   float site_quat[MJL_MAXSITE][4];
 };
+// What mjl_body_data (body_kernels.hip) reads beside the model block: body_iquat, the principal axes of the
+// descriptor's body-frame inertia tensor (the descriptor and ModelF hold the tensor, not MuJoCo's principal
+// moments + quaternion). Read for the ximat output only. Built by body_tab_build (model_host.h).
+struct BodyTab {
+  float iquat[MJL_MAXBODY][4];
+};
 // dim and stage of a sensor type (MJL_SENS_*)
 constexpr int sensor_type_dim(int type) {
   return type == MJL_SENS_FRAMEQUAT ? 4

@@ -192,6 +192,63 @@ inline void sensor_tab_build(const mjlModelDesc* d, SensorTab& t) {
     for (int i = 0; i < 4; i++) t.site_quat[s][i] = (float)d->site_quat[s][i];
 }
 
+// body_iquat of every body (BodyTab, model_dev.h): the principal axes of the body-frame tensor body_inertia by
+// cyclic Jacobi rotations in double. Convention (MuJoCo's): the moments in descending order along x, y, z of the
+// inertial frame, a proper rotation, quaternion with w >= 0. Moments that coincide leave the axes within their
+// eigenspace free; the iteration then keeps the body axes where the tensor is already diagonal (moments that
+// tie keep their body-frame order). `d` has passed model_check.
+inline void body_tab_build(const mjlModelDesc* d, BodyTab& t) {
+  std::memset(&t, 0, sizeof(t));
+  for (int b = 0; b < MJL_MAXBODY; b++) t.iquat[b][0] = 1.f;
+  for (int b = 1; b < d->nbody; b++) {
+    const double* in = d->body_inertia[b];
+    double A[3][3] = {{in[0], in[3], in[4]}, {in[3], in[1], in[5]}, {in[4], in[5], in[2]}};
+    double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    const double scale = std::fabs(in[0]) + std::fabs(in[1]) + std::fabs(in[2]);
+    for (int sweep = 0; sweep < 64; sweep++) {
+      if (std::fabs(A[0][1]) + std::fabs(A[0][2]) + std::fabs(A[1][2]) <= 1e-17 * scale) break;
+      for (int p = 0; p < 2; p++)
+        for (int q = p + 1; q < 3; q++) {
+          if (std::fabs(A[p][q]) <= 1e-300) continue;
+          const double theta = (A[q][q] - A[p][p]) / (2 * A[p][q]);
+          const double tt = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1));
+          const double c = 1 / std::sqrt(tt * tt + 1), s = tt * c;
+          for (int k = 0; k < 3; k++) {  // A <- A G, V <- V G
+            const double akp = A[k][p], akq = A[k][q], vkp = V[k][p], vkq = V[k][q];
+            A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq;
+            V[k][p] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq;
+          }
+          for (int k = 0; k < 3; k++) {  // A <- G' A
+            const double apk = A[p][k], aqk = A[q][k];
+            A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk;
+          }
+        }
+    }
+    int ord[3] = {0, 1, 2};  // descending moments, ties in body-frame order (insertion sort: stable)
+    for (int i = 1; i < 3; i++)
+      for (int j = i; j > 0 && A[ord[j]][ord[j]] > A[ord[j - 1]][ord[j - 1]]; j--) { int x = ord[j]; ord[j] = ord[j - 1]; ord[j - 1] = x; }
+    double R[3][3];
+    for (int i = 0; i < 3; i++)
+      for (int k = 0; k < 3; k++) R[i][k] = V[i][ord[k]];
+    const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
+                       R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
+    if (det < 0)
+      for (int i = 0; i < 3; i++) R[i][2] = -R[i][2];
+    double q[4];  // the largest of the four squared components leads (no cancellation)
+    const double tr = R[0][0] + R[1][1] + R[2][2];
+    if (tr > 0) {
+      const double s = 2 * std::sqrt(tr + 1);
+      q[0] = 0.25 * s; q[1] = (R[2][1] - R[1][2]) / s; q[2] = (R[0][2] - R[2][0]) / s; q[3] = (R[1][0] - R[0][1]) / s;
+    } else {
+      const int i = R[0][0] >= R[1][1] && R[0][0] >= R[2][2] ? 0 : (R[1][1] >= R[2][2] ? 1 : 2), j = (i + 1) % 3, k = (i + 2) % 3;
+      const double s = 2 * std::sqrt(1 + R[i][i] - R[j][j] - R[k][k]);
+      q[0] = (R[k][j] - R[j][k]) / s; q[1 + i] = 0.25 * s; q[1 + j] = (R[j][i] + R[i][j]) / s; q[1 + k] = (R[k][i] + R[i][k]) / s;
+    }
+    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]) * (q[0] < 0 ? -1.0 : 1.0);
+    for (int i = 0; i < 4; i++) t.iquat[b][i] = (float)(q[i] / n);
+  }
+}
+
 // Fills `f` (every byte) and the two capacities the row storage is sized with: the most constraint rows and
 // the most contacts one env can have. Returns MJL_OK, or an error code with its text in `msg`; `f` then
 // holds nothing of use.

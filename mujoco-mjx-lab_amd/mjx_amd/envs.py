@@ -128,6 +128,20 @@ class HumanoidEnv:
         from .mjx import sensors
         return sensors(self.sys, self.data, mask, stages, out)
 
+    def body_data(self, fields=("subtree_com",), mask: Optional[torch.Tensor] = None):
+        """Body-level fields of the envs' current state (mjx.body_data) in tensors this env owns: allocated
+        (zeros) at the first call that asks for a field and written again by every later one, so the same
+        BodyData comes back. Without a cfrc field it is one launch on the post-step state that can be captured
+        with the step, as sensors()."""
+        from .mjx import BODY_FIELDS, BodyData, body_data
+        fields = (fields,) if isinstance(fields, str) else tuple(fields)
+        bufs = self.__dict__.setdefault("_body_bufs", BodyData())
+        for f in fields:
+            if f in BODY_FIELDS and getattr(bufs, f) is None:
+                setattr(bufs, f, torch.zeros((self.num_envs, self.sys.nbody) + BODY_FIELDS[f], dtype=torch.float32,
+                                             device=self.obs.device))
+        return body_data(self.sys, self.data, fields, mask, bufs)
+
     def scan(self, frame, pattern, align: str = "pose", flg_static: bool = True, bodyexclude="self",
              cutoff: float = 0.0, mask: Optional[torch.Tensor] = None):
         """Range scan of the envs' current state (mjx.ray_scan): `pattern` = (lpnt, lvec) [nray, 3] in the frame
@@ -254,6 +268,20 @@ class HumanoidEnv:
             from .render import Renderer
             self._renderer = Renderer(self.sys, self.num_envs, self.data.device.index or 0)
         return self._renderer.render(self.data.get("qpos"), camera, width, height, shadows, rgb, depth, seg)
+
+
+def gym_humanoid_obs(sys: Model, d: Data, body) -> torch.Tensor:
+    """The Gym Humanoid observation of every env, [nenv, (nq - 2) + nv + 10 (nbody - 1) + 6 (nbody - 1) + nv +
+    6 (nbody - 1)]: qpos[2:], qvel, cinert[1:], cvel[1:], qfrc_actuator, cfrc_ext[1:] in Gym's order, from `d`
+    and a mjx.BodyData holding cinert, cvel and cfrc_ext of the same state (asking for cfrc_ext runs the forward
+    pass that also leaves qfrc_actuator). Plain torch; the trainers do not use it."""
+    for f in ("cinert", "cvel", "cfrc_ext"):
+        if getattr(body, f) is None:
+            raise MjlError(f"gym_humanoid_obs needs body.{f} (mjx.body_data(..., fields=('cinert', 'cvel', 'cfrc_ext')))")
+    n = d.nenv
+    return torch.cat([d.get("qpos")[:, 2:], d.get("qvel"), body.cinert[:, 1:].reshape(n, -1),
+                      body.cvel[:, 1:].reshape(n, -1), d.get("qfrc_actuator"), body.cfrc_ext[:, 1:].reshape(n, -1)],
+                     dim=1)
 
 
 class EnvState(NamedTuple):

@@ -293,6 +293,62 @@ def sensors(sys: Model, d: Data, mask: Optional[torch.Tensor] = None, stages: Op
     return out
 
 
+@dataclass
+class BodyData:
+    """The body-level half of mjx.Data with a leading env axis (body_data): each field [nenv, nbody, ...] or
+    None where it was not asked for. World frame; see include/mjx355.h mjl_body_data for the definitions."""
+    xipos: Optional[torch.Tensor] = None           # [nenv, nbody, 3]
+    ximat: Optional[torch.Tensor] = None           # [nenv, nbody, 3, 3]
+    subtree_com: Optional[torch.Tensor] = None     # [nenv, nbody, 3]
+    cinert: Optional[torch.Tensor] = None          # [nenv, nbody, 10]
+    cvel: Optional[torch.Tensor] = None            # [nenv, nbody, 6]: angular, linear
+    subtree_linvel: Optional[torch.Tensor] = None  # [nenv, nbody, 3]
+    subtree_angmom: Optional[torch.Tensor] = None  # [nenv, nbody, 3]
+    cfrc_ext: Optional[torch.Tensor] = None        # [nenv, nbody, 6]: torque, force
+    cfrc_int: Optional[torch.Tensor] = None        # [nenv, nbody, 6]: torque, force
+
+
+# mjl_body_data's outputs in argument order, with the trailing shape of each
+BODY_FIELDS = {"xipos": (3,), "ximat": (3, 3), "subtree_com": (3,), "cinert": (10,), "cvel": (6,),
+               "subtree_linvel": (3,), "subtree_angmom": (3,), "cfrc_ext": (6,), "cfrc_int": (6,)}
+
+
+def body_data(sys: Model, d: Data, fields=("subtree_com",), mask: Optional[torch.Tensor] = None,
+              out: Optional[BodyData] = None) -> BodyData:
+    """Body-level fields of the current state: any of xipos, ximat, subtree_com, cinert, cvel, subtree_linvel,
+    subtree_angmom, cfrc_ext, cfrc_int (BODY_FIELDS), as MuJoCo / MJX define them. Without a cfrc field the call
+    is one launch that reads qpos / qvel only (the call to make after an env step, capturable); with one it runs
+    mjx.forward on the envs with mask > 0.5 first and reads that pass's qacc and contacts. Masses and inertias
+    are the env's own while per-env model parameters are on. out: a BodyData whose tensors of `fields` are
+    written into (rows of envs outside the mask keep their content); fresh tensors are zeros under a mask. See
+    include/mjx355.h mjl_body_data."""
+    fields = (fields,) if isinstance(fields, str) else tuple(fields)
+    unknown = [f for f in fields if f not in BODY_FIELDS]
+    if unknown:
+        raise MjlError(f"unknown body_data field {unknown} (known: {list(BODY_FIELDS)})")
+    if not fields:
+        raise MjlError("body_data needs at least one field")
+    res = BodyData() if out is None else out
+    ptrs = []
+    for name, tail in BODY_FIELDS.items():
+        if name not in fields:
+            ptrs.append(None)
+            continue
+        shape = (d.nenv, sys.nbody) + tail
+        t = getattr(res, name)
+        if t is None:
+            if out is not None:
+                raise MjlError(f"out.{name} is None but {name} was asked for")
+            t = (torch.empty if mask is None else torch.zeros)(shape, dtype=torch.float32, device=d.device)
+            setattr(res, name, t)
+        elif tuple(t.shape) != shape or t.device != d.device:
+            raise MjlError(f"out.{name} must have shape {shape} on {d.device}")
+        ptrs.append(_ptr(t))
+    mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
+    check(lib().mjl_body_data(d.handle, _ptr(mk), *ptrs, _stream()))
+    return res
+
+
 def _body_arg(sys: Model, body, carrying: int = -1) -> int:
     """bodyexclude as the library takes it: an id (-1: none), a body name, or "self" (the carrying body)."""
     if isinstance(body, str):
