@@ -1570,6 +1570,12 @@ template <class D, bool G> PHASE bool build_rows(MP m_, LDSA WS<D>* W, Rows<G> R
         R.J[(r0 + 2) * LD + d] = vn + mu * vt2;
         R.J[(r0 + 3) * LD + d] = vn - mu * vt2;
       }
+      // the pad columns 32 .. LD - 1 (LD = 36): the row dots run over all LD entries, and a row's storage
+      // holds whatever was there before (the smooth-dynamics scratch in LDS, an older slab in global memory)
+      if constexpr (LD > 32) {
+        if (d < LD - 32)
+          for (int q = 0; q < (dim == 1 ? 1 : 4); q++) R.J[(r0 + q) * LD + 32 + d] = 0.f;
+      }
     }
   }
   SYNC();

@@ -16,8 +16,8 @@ efc_force, jointactuatorfrc through qfrc_actuator, the accelerometer through qac
 compared with the reference evaluated on the qacc the call's forward pass stored, at the 8 x yardstick bound
 alone (about 9e-4 m/s^2): that takes the forward's error out and checks gravity and the centripetal / Coriolis
 terms, which the test asserts are more than 100 x that bound in every moving state. framequat is compared up to sign (q and -q
-are one rotation). The generic (non-humanoid) kernel instantiation is not run on the GPU by the existing suite,
-but the CPU tests' small chain model (a free root with a rotated body, joint pos offsets, two joints on one body,
+are one rotation). The generic (non-humanoid) kernel instantiation runs in tests/test_generic_gpu.py, this
+readout included (test_sensors_readout_on_tail); the CPU tests' small chain model (a free root with a rotated body, joint pos offsets, two joints on one body,
 a site quaternion) fits the humanoid instantiation the existing small-model GPU tests run, so it is run here
 too, with every sensor type once."""
 import ctypes as C
