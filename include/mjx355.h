@@ -398,6 +398,16 @@ int mjl_ray_scan(mjlBatch* batch, const float* mask, int objtype, int objid, int
  * -> forward + integrate, state updated in place. */
 int mjl_step(mjlBatch* batch, const float* ctrl, void* stream);
 
+/* Physics substeps: the state and the stored derived fields that nstep consecutive mjl_step(batch, ctrl) leave,
+ * in one call. The same ctrl holds for every substep (NULL = the stored one), and so do attached applied forces;
+ * per-env model blocks are honoured; an env whose rows overflow in one substep takes the global path for that
+ * substep only. The call issues nstep single-step launches on the stream (a fused launch that kept the state on
+ * chip measured slower and was dropped: DESIGN.md section 3, "Substeps"); nstep == 1 is mjl_step.
+ * No allocation, no synchronisation, capturable. Not differentiated: the VJP, record and replay entries stay
+ * single-step. MJL_ERR_ARG: null batch, nstep outside 1..MJL_MAXSUBSTEP (the state is left untouched). */
+#define MJL_MAXSUBSTEP 64
+int mjl_step_n(mjlBatch* batch, const float* ctrl, int nstep, void* stream);
+
 /* Speed-test step (mjx_humanoid_speed_test.py:48-57): for each env e, a fresh make_data state
  * with qvel[0] = vel[e], one step, out[e] = new qpos[0]. Stateless: does not touch the batch
  * state (the batch only provides scratch and the model). */
@@ -413,6 +423,18 @@ int mjl_env_config(mjlBatch* batch, const mjlEnvConfig* cfg);
  * the post-reset observation, exactly as merge_if_done does; rew/term/trunc stay the step's. */
 int mjl_env_step(mjlBatch* batch, const float* act, float* obs, float* rew, float* term,
                  float* trunc, int auto_reset, uint64_t seed, uint64_t counter, void* stream);
+
+/* A control step of nstep physics steps (Brax's n_frames, Gym's frame_skip): single_step of src/envs.py with
+ * mjx.step applied nstep times. The result is that of ctrl = clip(flip ? act[act_perm] * act_sign : act, -1, 1)
+ * (flip from the pre-step aux[0]), nstep - 1 mjl_step(ctrl), then one mjl_env_step(act, ...): reward,
+ * observation, termination, the NaN flag and the stance logic are evaluated once, after the last substep, from
+ * that substep's forward pass. aux[8] (the episode step) advances by 1, time by nstep * timestep; the reward's
+ * dt stays opt.timestep. Auto-reset, reset pool, key-drawn resets and the counter base as in mjl_env_step, one
+ * (seed, counter) draw per call. Applied forces, per-env models and the global-rows path as in mjl_step_n.
+ * nstep == 1 is mjl_env_step. No allocation, no synchronisation, capturable. Not differentiated.
+ * MJL_ERR_ARG: null batch or outputs, nstep outside 1..MJL_MAXSUBSTEP, mjl_env_config not called. */
+int mjl_env_step_n(mjlBatch* batch, const float* act, int nstep, float* obs, float* rew, float* term,
+                   float* trunc, int auto_reset, uint64_t seed, uint64_t counter, void* stream);
 
 /* Reset pool: the v_reset half of train_ppo.py:147-161's merge_if_done, moved off the step's
  * critical path. A reset does not depend on the state it replaces, so resets can be computed in bulk

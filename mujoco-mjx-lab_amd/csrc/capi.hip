@@ -13,6 +13,7 @@
 #include <string>
 
 #include "step_kernels.hip"
+#include "substep_kernels.hip"
 #include "adjoint.hip"
 #include "ppo_kernels.hip"
 #include "apg_kernels.hip"
@@ -696,6 +697,16 @@ int mjl_step(mjlBatch* B, const float* ctrl, void* stream) {
   return launch<MODE_STEP, true>(B, P, stream);
 }
 
+int mjl_step_n(mjlBatch* B, const float* ctrl, int nstep, void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (nstep < 1 || nstep > MJL_MAXSUBSTEP) return fail(MJL_ERR_ARG, "nstep = %d outside 1..%d", nstep, MJL_MAXSUBSTEP);
+  // nstep single-step launches (see substep_kernels.hip); the first stores ctrl, the others run the stored one
+  if (int rc = mjl_step(B, ctrl, stream)) return rc;
+  for (int s = 1; s < nstep; s++)
+    if (int rc = mjl_step(B, nullptr, stream)) return rc;
+  return MJL_OK;
+}
+
 int mjl_speedtest_step(mjlBatch* B, const float* vel, float* out, void* stream) {
   if (!B || !vel || !out) return fail(MJL_ERR_ARG, "bad argument");
   KParams P = make_params(B);
@@ -750,6 +761,25 @@ int mjl_env_step(mjlBatch* B, const float* act, float* obs, float* rew, float* t
   set_seed_counter(P, seed, counter);
   if (B->d_pool_ctl && auto_reset) { P.rs = B->rs; P.rs_obs = B->rs_obs; P.pool_ctl = B->d_pool_ctl; }
   return launch<MODE_ENV_STEP, true>(B, P, stream);
+}
+
+int mjl_env_step_n(mjlBatch* B, const float* act, int nstep, float* obs, float* rew, float* term, float* trunc,
+                   int auto_reset, uint64_t seed, uint64_t counter, void* stream) {
+  if (!B || !act || !obs || !rew || !term || !trunc) return fail(MJL_ERR_ARG, "bad argument");
+  if (nstep < 1 || nstep > MJL_MAXSUBSTEP) return fail(MJL_ERR_ARG, "nstep = %d outside 1..%d", nstep, MJL_MAXSUBSTEP);
+  if (!B->has_env) return fail(MJL_ERR_ARG, "mjl_env_config not called");
+  if (nstep > 1) {  // the flipped and clipped action into the batch's ctrl, nstep - 1 plain steps on it
+    HIPCHK(hipSetDevice(B->device));
+    const int nu = B->model->desc.nu, n = B->nenv * nu;
+    if (n > 0) {
+      hipLaunchKernelGGL(env_ctrl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B->d_env,
+                         act, B->s.aux, B->s.ctrl, B->nenv, nu);
+      HIPCHK(hipGetLastError());
+    }
+    for (int s = 1; s < nstep; s++)
+      if (int rc = mjl_step(B, nullptr, stream)) return rc;
+  }
+  return mjl_env_step(B, act, obs, rew, term, trunc, auto_reset, seed, counter, stream);
 }
 
 int mjl_env_fill_reset_pool(mjlBatch* B, const int* dev_n, uint64_t seed, uint64_t counter, void* stream) {

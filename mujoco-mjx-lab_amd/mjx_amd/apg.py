@@ -673,6 +673,10 @@ class HumanoidAPGEnv:
         from . import abi
         if vjp not in ("implicit", "unrolled"):
             raise ValueError(f"vjp must be 'implicit' or 'unrolled', not {vjp!r}")
+        if getattr(env, "n_frames", 1) != 1:
+            raise ValueError(f"APG needs n_frames = 1, not {env.n_frames}: the step VJP, record and replay "
+                             "entries differentiate one physics step per env step (fused substeps are not "
+                             "differentiated)")
         self.vjp = vjp
         self.vjp_carries_ws = vjp == "unrolled"  # jax.grad also differentiates the carried warm start
         env.data.set_option(abi.OPT_VJP_UNROLLED, int(vjp == "unrolled"))

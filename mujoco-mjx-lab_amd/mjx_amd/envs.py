@@ -46,7 +46,14 @@ class HumanoidEnv:
     """`num_envs` walker envs resident on one GPU. State lives in `self.data` (native batch)."""
 
     def __init__(self, sys: Model, cfg: EnvConfig, num_envs: int, device: int = 0, seed: int = 0,
-                 store_derived: bool = False):
+                 store_derived: bool = False, n_frames: int = 1):
+        """n_frames: physics steps per step() (Brax's n_frames, Gym's frame_skip), one mjl_env_step_n call:
+        the action holds for all of them and reward, observation and termination are evaluated once, after
+        the last; `dt` = n_frames * timestep is the control period (the reward's own dt stays the timestep)."""
+        if not 1 <= int(n_frames) <= abi.MAXSUBSTEP:
+            raise MjlError(f"n_frames must be in 1..{abi.MAXSUBSTEP}, not {n_frames}")
+        self.n_frames = int(n_frames)
+        self.dt = self.n_frames * float(sys.m.timestep)
         self.sys = sys
         self.cfg = cfg
         self.num_envs = int(num_envs)
@@ -200,9 +207,9 @@ class HumanoidEnv:
         if act.shape != (self.num_envs, self.act_dim):
             raise MjlError(f"action must have shape {(self.num_envs, self.act_dim)}")
         obs, rew, term, trunc = out if out is not None else (self.obs, self.rew, self.term, self.trunc)
-        check(lib().mjl_env_step(self.data.handle, _ptr(act), _ptr(obs), _ptr(rew), _ptr(term), _ptr(trunc),
-                                 int(auto_reset), self.seed, self._next_counter() if counter is None else int(counter),
-                                 _stream()))
+        check(lib().mjl_env_step_n(self.data.handle, _ptr(act), self.n_frames, _ptr(obs), _ptr(rew), _ptr(term),
+                                   _ptr(trunc), int(auto_reset), self.seed,
+                                   self._next_counter() if counter is None else int(counter), _stream()))
         return obs, rew, term, trunc
 
     def step_vjp(self, act: torch.Tensor, g_qpos: torch.Tensor, g_qvel: torch.Tensor, g_rew: torch.Tensor,

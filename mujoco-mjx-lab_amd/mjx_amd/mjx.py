@@ -458,12 +458,16 @@ def ray_scan(sys: Model, d: Data, frame, lpnt, lvec, align: str = "pose", flg_st
     return dist, geomid, hitpos
 
 
-def step(sys: Model, d: Data, ctrl: Optional[torch.Tensor] = None) -> Data:
+def step(sys: Model, d: Data, ctrl: Optional[torch.Tensor] = None, nstep: int = 1) -> Data:
+    """mjx.step, `nstep` times in one call (mjl_step_n): the same ctrl (None: the stored one) holds for every
+    substep, and the state and derived fields are those `nstep` single steps leave. Not differentiated."""
+    if not 1 <= int(nstep) <= abi.MAXSUBSTEP:
+        raise MjlError(f"nstep must be in 1..{abi.MAXSUBSTEP}, not {nstep}")
     if ctrl is not None:
         ctrl = ctrl.to(device=d.device, dtype=torch.float32).contiguous()
         if ctrl.shape != (d.nenv, sys.nu):
             raise MjlError(f"ctrl must have shape {(d.nenv, sys.nu)}")
-    check(lib().mjl_step(d.handle, _ptr(ctrl), _stream()))
+    check(lib().mjl_step_n(d.handle, _ptr(ctrl), int(nstep), _stream()))
     return d
 
 

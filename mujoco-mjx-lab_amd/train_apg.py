@@ -65,7 +65,12 @@ def main():
                     help="carry a per-env power-of-two exponent beside the reverse sweep's cotangents, so envs whose "
                          "chained step Jacobians leave fp32 range stay in the gradient (DESIGN.md 3b); off: the "
                          "guard cuts them (reverse_nonfinite_envs)")
+    ap.add_argument("--n-frames", type=int, default=1, metavar="K",
+                    help="physics steps per env step: APG takes 1 only (fused substeps are not differentiated)")
     a = ap.parse_args()
+    if a.n_frames != 1:
+        ap.error("--n-frames must be 1 for APG: the step VJP, record and replay entries differentiate one physics "
+                 "step per env step (fused substeps are not differentiated); train_ppo.py takes --n-frames K")
 
     cfg = APGConfig()
     for k in ("batch_size", "horizon", "lr", "seed"):

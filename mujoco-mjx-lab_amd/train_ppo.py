@@ -54,7 +54,12 @@ def parse_args(argv=None):
                          "(off by default)")
     ap.add_argument("--action-scale", type=float, default=None, metavar="S",
                     help="radians of joint target per unit action with --pd-control (default 1)")
+    ap.add_argument("--n-frames", type=int, default=1, metavar="K",
+                    help="physics steps per env step, in the training and evaluation envs (the "
+                         "action holds for all K, reward and observation come from the last; default 1)")
     a = ap.parse_args(argv)
+    if not 1 <= a.n_frames <= 64:
+        ap.error("--n-frames must be in 1..64")
     if a.action_scale is not None and a.pd_control is None:
         ap.error("--action-scale needs --pd-control KP KV")
     if a.push_force is None and (a.push_interval or a.push_duration is not None or a.push_body):
@@ -116,8 +121,10 @@ def main():
     model = control_model(a, mjx_amd.load_model(a.model or os.path.splitext(os.path.basename(cfg.xml_path))[0]))
     sys_ = mjx.put_model(model)
     env_cfg = resolve_ids(model, cfg.env_config)
-    env = HumanoidEnv(sys_, env_cfg, cfg.num_envs // world, device=local, seed=cfg.seed * 7919 + rank)
-    eval_env = HumanoidEnv(sys_, env_cfg, 32, device=local, seed=cfg.seed + 10000) if rank == 0 else None
+    env = HumanoidEnv(sys_, env_cfg, cfg.num_envs // world, device=local, seed=cfg.seed * 7919 + rank,
+                      n_frames=a.n_frames)
+    eval_env = HumanoidEnv(sys_, env_cfg, 32, device=local, seed=cfg.seed + 10000,
+                           n_frames=a.n_frames) if rank == 0 else None
     out = None
     if rank == 0:
         out = os.path.join(cfg.results_dir, time.strftime("%Y%m%d_%H%M%S") + "_ppo")
