@@ -358,6 +358,48 @@ int mjl_body_data(mjlBatch* batch, const float* mask,
                   float* cfrc_ext, float* cfrc_int,                                    /* acc */
                   void* stream);
 
+/* Point Jacobians of the batch's current state: mj_jac / mjx's support.jac for npoint points per env, each carried
+ * by a body. Buffers (float32 / int32, device, read at execution time): body [npoint], shared by all envs; jacp,
+ * jacr [nenv, npoint, 3, nv] row-major (MuJoCo's 3 x nv layout), either may be NULL, not both; xpnt
+ * [nenv, npoint, 3], the world point used, or NULL.
+ *   MJL_JAC_WORLD  pnt [nenv, npoint, 3]: world points, as in mj_jac(m, d, point, body).
+ *   MJL_JAC_LOCAL  pnt [npoint, 3]: offsets in the body's frame, the world point is xpos_b + R_b pnt; NULL: the
+ *                  body origins. A site is its body with pnt = site_pos.
+ * Poses: forward kinematics of the batch's current qpos, run in the same launch, the free joint's quaternion
+ * normalised as the step normalises it (the rays' rule). No mjl_forward is needed first, the stored xpos / xquat
+ * are neither read nor written, so the call is correct right after mjl_env_step. Per-env model parameters and
+ * applied forces do not matter (no geometric field is per-env).
+ * Column d is zero unless dof d moves the body (a dof of the body or of one of its ancestors). For such a dof,
+ * with x the point:
+ *   hinge, world axis a through the world anchor p     jacr[:, d] = a         jacp[:, d] = a x (x - p)
+ *   free joint, translation i                          jacr[:, d] = 0         jacp[:, d] = e_i
+ *   free joint, rotation i (body-local rates)          jacr[:, d] = R_b e_i   jacp[:, d] = (R_b e_i) x (x - xpos_b)
+ * so jacp qvel is the world velocity of the point and jacr qvel the body's angular velocity: what mjl_sensors
+ * (framelinvel, frameangvel) and mjl_body_data (cvel) report. Body 0 gives zero rows. A body id outside
+ * 0..nbody-1 gives NaN rows in jacp, jacr and xpnt (mjl_gather_rows' rule for a bad index).
+ * Envs with mask <= 0.5 keep their rows (mask NULL = all envs). One launch, no allocation, no synchronisation,
+ * capturable. MJL_ERR_ARG: a null batch or body; jacp and jacr both NULL; npoint outside 1..256; an unknown frame;
+ * pnt NULL with MJL_JAC_WORLD. */
+enum { MJL_JAC_WORLD = 0, MJL_JAC_LOCAL = 1 };
+int mjl_jac(mjlBatch* batch, const float* mask, int npoint, const int32_t* body, int frame, const float* pnt,
+            float* jacp, float* jacr, float* xpnt, void* stream);
+
+/* The joint-space inertia of the batch's current qpos, products and solves with it: mj_fullM / support.full_m,
+ * support.mul_m and smooth.solve_m. Buffers (float32, device): full_m [nenv, nv, nv], dense; vec, mul_m, solve_m
+ * [nenv, nvec, nv]. Any output may be NULL, not all three; vec is required with mul_m or solve_m; nvec in 0..64,
+ * 0 only with full_m alone.
+ *   full_m[e]      M_e: the composite-rigid-body matrix, dof_armature on the diagonal; symmetric bit for bit
+ *   mul_m[e, k]    M_e vec[e, k]
+ *   solve_m[e, k]  M_e^-1 vec[e, k], by a Cholesky factor of M_e computed in the kernel
+ * Poses as mjl_jac: forward kinematics of the current qpos in the same launch, nothing of the batch read but qpos
+ * or written. While MJL_OPT_PER_ENV_MODEL is on, env e uses its own block's body_mass, body_inertia, body_ipos
+ * and dof_armature.
+ * Envs with mask <= 0.5 keep their rows (mask NULL = all envs). One launch, no allocation, no synchronisation,
+ * capturable. MJL_ERR_ARG: a null batch; every output NULL; nvec outside 0..64; mul_m or solve_m with vec NULL or
+ * nvec = 0. */
+int mjl_mass_matrix(mjlBatch* batch, const float* mask, float* full_m, int nvec, const float* vec, float* mul_m,
+                    float* solve_m, void* stream);
+
 /* Ray casts against the batch's current state: mjx.ray / mj_ray (mjl_ray, caller-chosen world rays per env) and
  * ray patterns carried by a body or site frame (mjl_ray_scan: height scanner, lidar fan, rangefinder).
  * Buffers (float32 / int32, device): mjl_ray pnt, vec [nenv, nray, 3] in the world frame; mjl_ray_scan lpnt, lvec

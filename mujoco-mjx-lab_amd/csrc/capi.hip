@@ -23,6 +23,7 @@
 #include "contact_kernels.hip"
 #include "sensor_kernels.hip"
 #include "body_kernels.hip"
+#include "dyn_kernels.hip"
 #include "ray_kernels.hip"
 #include "model_host.h"
 
@@ -56,6 +57,7 @@ struct mjlModel {
   ModelF mf;
   SensorTab st;  // the readout table of mjl_sensors (st.n = 0: the model has none)
   BodyTab bt;    // body_iquat, for mjl_body_data's ximat
+  DynTab dt;     // body_dofmask, for mjl_jac's columns
   int nefc_max, ncon_max, nvc;  // nvc: 0 = DHum kernels, 1 = DGen kernels
 };
 
@@ -116,6 +118,7 @@ struct mjlBatch {
   ParamStage* d_param_stage;  // what model_params_kernel needs beside the blocks (allocated with them)
   SensorTab* d_sensors;       // the readout table beside the model block, or null (a model without readout sensors)
   BodyTab* d_bodytab;         // body_iquat beside the model block (mjl_body_data)
+  DynTab* d_dyntab;           // body_dofmask beside the model block (mjl_jac)
   int ray_chunk;              // MJL_OPT_RAY_CHUNK: rays per wavefront of mjl_ray / mjl_ray_scan, 0 = kRayChunk
 };
 
@@ -158,6 +161,7 @@ int mjl_model_create(const mjlModelDesc* d, mjlModel** out) {
   M->desc = *d;
   sensor_tab_build(d, M->st);
   body_tab_build(d, M->bt);
+  dyn_tab_build(d, M->dt);
   // compact kernel instantiation when the model fits the humanoid capacities, generic otherwise
   M->nvc = (d->nv <= DHum::NV && d->nbody <= DHum::NB && d->njnt <= DHum::NJ && d->ngeom <= DHum::NG) ? 0 : 1;
   *out = M.release();
@@ -219,6 +223,8 @@ int mjl_batch_create(const mjlModel* model, int nenv, int device, mjlBatch** out
   }
   if (e == hipSuccess) e = hipMalloc(&B->d_bodytab, sizeof(BodyTab));
   if (e == hipSuccess) e = hipMemcpy(B->d_bodytab, &model->bt, sizeof(BodyTab), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc(&B->d_dyntab, sizeof(DynTab));
+  if (e == hipSuccess) e = hipMemcpy(B->d_dyntab, &model->dt, sizeof(DynTab), hipMemcpyHostToDevice);
   // global overflow rows for envs whose active constraints exceed the LDS capacity
   int LD = model->nvc == 0 ? DHum::LD : DGen::LD;
   B->gmax_efc = model->nefc_max > 0 ? model->nefc_max : 1;
@@ -228,7 +234,7 @@ int mjl_batch_create(const mjlModel* model, int nenv, int device, mjlBatch** out
   if (e == hipSuccess) e = hipMalloc(&B->d_scratch, (size_t)B->scratch_stride * nenv * sizeof(float));
   if (e != hipSuccess) {
     (void)hipFree(B->d_state); (void)hipFree(B->d_model); (void)hipFree(B->d_env); (void)hipFree(B->d_scratch);
-    (void)hipFree(B->d_sensors); (void)hipFree(B->d_bodytab);
+    (void)hipFree(B->d_sensors); (void)hipFree(B->d_bodytab); (void)hipFree(B->d_dyntab);
     delete B;
     return fail(MJL_ERR_HIP, "batch allocation: %s", hipGetErrorString(e));
   }
@@ -245,7 +251,7 @@ void mjl_batch_destroy(mjlBatch* B) {
   (void)hipFree(B->d_exp_stage);
   (void)hipFree(B->d_rs); (void)hipFree(B->d_pool_ctl); (void)hipFree(B->d_vtape);
   (void)hipFree(B->d_model_env); (void)hipFree(B->d_param_stage);
-  (void)hipFree(B->d_sensors); (void)hipFree(B->d_bodytab);
+  (void)hipFree(B->d_sensors); (void)hipFree(B->d_bodytab); (void)hipFree(B->d_dyntab);
   delete B;
 }
 
@@ -626,6 +632,45 @@ int mjl_body_data(mjlBatch* B, const float* mask, float* xipos, float* ximat, fl
     hipLaunchKernelGGL(body_data_kernel<DHum>, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
   else
     hipLaunchKernelGGL(body_data_kernel<DGen>, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
+}
+
+// One launch each (dyn_kernels.hip): forward kinematics of the current qpos inside the kernel, nothing of the
+// batch written.
+int mjl_jac(mjlBatch* B, const float* mask, int npoint, const int32_t* body, int frame, const float* pnt, float* jacp,
+            float* jacr, float* xpnt, void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (!body) return fail(MJL_ERR_ARG, "mjl_jac: body is required");
+  if (!jacp && !jacr) return fail(MJL_ERR_ARG, "mjl_jac: jacp and jacr are both NULL");
+  if (npoint < 1 || npoint > 256) return fail(MJL_ERR_ARG, "mjl_jac: npoint = %d outside 1..256", npoint);
+  if (frame != MJL_JAC_WORLD && frame != MJL_JAC_LOCAL)
+    return fail(MJL_ERR_ARG, "mjl_jac: frame = %d: MJL_JAC_WORLD or MJL_JAC_LOCAL", frame);
+  if (frame == MJL_JAC_WORLD && !pnt) return fail(MJL_ERR_ARG, "mjl_jac: pnt is required with MJL_JAC_WORLD");
+  HIPCHK(hipSetDevice(B->device));
+  JacArgs A;
+  A.m = B->d_model; A.tab = B->d_dyntab; A.qpos = B->s.qpos; A.mask = mask;
+  A.nenv = B->nenv; A.npoint = npoint; A.frame = frame; A.body = body; A.pnt = pnt;
+  A.jacp = jacp; A.jacr = jacr; A.xpnt = xpnt;
+  hipLaunchKernelGGL(jac_kernel, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
+}
+
+int mjl_mass_matrix(mjlBatch* B, const float* mask, float* full_m, int nvec, const float* vec, float* mul_m,
+                    float* solve_m, void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (!full_m && !mul_m && !solve_m) return fail(MJL_ERR_ARG, "mjl_mass_matrix: every output is NULL");
+  if (nvec < 0 || nvec > 64) return fail(MJL_ERR_ARG, "mjl_mass_matrix: nvec = %d outside 0..64", nvec);
+  if (mul_m || solve_m) {
+    if (!vec) return fail(MJL_ERR_ARG, "mjl_mass_matrix: vec is required with mul_m or solve_m");
+    if (nvec < 1) return fail(MJL_ERR_ARG, "mjl_mass_matrix: nvec = 0 with mul_m or solve_m");
+  }
+  HIPCHK(hipSetDevice(B->device));
+  MassArgs A;
+  A.m = B->d_model; A.m_env = B->d_model_env; A.qpos = B->s.qpos; A.mask = mask;
+  A.nenv = B->nenv; A.nvec = nvec; A.vec = vec; A.full_m = full_m; A.mul_m = mul_m; A.solve_m = solve_m;
+  hipLaunchKernelGGL(mass_matrix_kernel, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
   HIPCHK(hipGetLastError());
   return MJL_OK;
 }

@@ -171,6 +171,12 @@ struct SensorTab {
 struct BodyTab {
   float iquat[MJL_MAXBODY][4];
 };
+// What mjl_jac (dyn_kernels.hip) reads beside the model block: bit k of body_dofmask[b] set <=> dof k moves body b
+// (the dofs of b and of its ancestors), the columns of b's Jacobian that are not zero. Row 0 is 0. Built by
+// dyn_tab_build (model_host.h).
+struct DynTab {
+  uint32_t body_dofmask[MJL_MAXBODY];
+};
 // dim and stage of a sensor type (MJL_SENS_*)
 constexpr int sensor_type_dim(int type) {
   return type == MJL_SENS_FRAMEQUAT ? 4

@@ -249,6 +249,15 @@ inline void body_tab_build(const mjlModelDesc* d, BodyTab& t) {
   }
 }
 
+// body_dofmask of every body (DynTab, model_dev.h): the dofs of the body and of its ancestors, as model_build
+// derives it for the pairs' PairRec.mask1 / mask2. `d` has passed model_check.
+inline void dyn_tab_build(const mjlModelDesc* d, DynTab& t) {
+  std::memset(&t, 0, sizeof(t));
+  for (int b = 1; b < d->nbody; b++)
+    for (int bb = b; bb > 0; bb = d->body_parentid[bb])
+      for (int k = d->body_dofadr[bb]; k < d->body_dofadr[bb] + d->body_dofnum[bb]; k++) t.body_dofmask[b] |= 1u << k;
+}
+
 // Fills `f` (every byte) and the two capacities the row storage is sized with: the most constraint rows and
 // the most contacts one env can have. Returns MJL_OK, or an error code with its text in `msg`; `f` then
 // holds nothing of use.

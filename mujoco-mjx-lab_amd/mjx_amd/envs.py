@@ -149,6 +149,32 @@ class HumanoidEnv:
                                              device=self.obs.device))
         return body_data(self.sys, self.data, fields, mask, bufs)
 
+    def jac(self, frames, offset=None, mask: Optional[torch.Tensor] = None):
+        """Jacobians of points fixed in body or site frames of the envs' current state (mjx.jac_local): (jacp,
+        jacr, xpnt) in tensors this env owns. The frames' device tables and the three outputs are allocated
+        (zeros) at the first call with these (frames, offset) and written again by every later one, so after one
+        eager call it is one launch on the post-step state that can be captured with the step, as sensors()."""
+        from .mjx import jac_frames, jac_local
+        bodies, local = jac_frames(self.sys, frames, offset)
+        key = (tuple(bodies), local.tobytes())
+        bufs = self.__dict__.setdefault("_jac_bufs", {})
+        if key not in bufs:
+            dev, n, p, nv = self.obs.device, self.num_envs, len(bodies), self.sys.nv
+            bufs[key] = ((torch.tensor(bodies, dtype=torch.int32, device=dev), torch.tensor(local, device=dev)),
+                         (torch.zeros((n, p, 3, nv), device=dev), torch.zeros((n, p, 3, nv), device=dev),
+                          torch.zeros((n, p, 3), device=dev)))
+        tabs, out = bufs[key]
+        return jac_local(self.sys, self.data, frames, offset, mask, out, _dev=tabs)
+
+    def full_m(self, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The joint-space inertia [num_envs, nv, nv] of the envs' current state (mjx.full_m) in a tensor this env
+        owns (zeros at first, written again by every call): one launch on the post-step state, capturable with
+        the step."""
+        from .mjx import full_m
+        if getattr(self, "_full_m", None) is None:
+            self._full_m = torch.zeros((self.num_envs, self.sys.nv, self.sys.nv), device=self.obs.device)
+        return full_m(self.sys, self.data, mask, self._full_m)
+
     def scan(self, frame, pattern, align: str = "pose", flg_static: bool = True, bodyexclude="self",
              cutoff: float = 0.0, mask: Optional[torch.Tensor] = None):
         """Range scan of the envs' current state (mjx.ray_scan): `pattern` = (lpnt, lvec) [nray, 3] in the frame

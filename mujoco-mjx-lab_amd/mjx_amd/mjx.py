@@ -458,6 +458,165 @@ def ray_scan(sys: Model, d: Data, frame, lpnt, lvec, align: str = "pose", flg_st
     return dist, geomid, hitpos
 
 
+MAX_JAC_POINTS = 256  # mjl_jac's npoint
+
+
+def _as_list(x) -> list:
+    return list(x) if isinstance(x, (list, tuple)) else [x]
+
+
+def _jac_bodies(sys: Model, body) -> list:
+    """Body ids of `body` (an id, a name, or a list of either), checked against the model on the host."""
+    ids = []
+    for b in _as_list(body):
+        if isinstance(b, str):
+            i = sys.m.name2id("body", b)
+            if i < 0:
+                raise ValueError(f"no body named {b!r}")
+        else:
+            i = int(b)
+        if not 0 <= i < sys.nbody:
+            raise ValueError(f"body id {i} outside 0..{sys.nbody - 1}")
+        ids.append(i)
+    if not 1 <= len(ids) <= MAX_JAC_POINTS:
+        raise ValueError(f"jac takes 1..{MAX_JAC_POINTS} points, not {len(ids)}")
+    return ids
+
+
+def jac_frames(sys: Model, frame, offset=None):
+    """(body ids, local offsets [npoint, 3] float32 numpy) of jac_local's frames: a body or site as scan_frame
+    resolves it (a name, bodies first, or an ("xbody" | "site", id) pair), or a list of them; a site is its
+    body at site_pos. offset ([3] or [npoint, 3], in the body's frame, or the site's for a site) is added."""
+    import numpy as np
+    single = isinstance(frame, str) or (isinstance(frame, tuple) and len(frame) == 2 and isinstance(frame[0], str)
+                                        and frame[0] in ("xbody", "site") and not isinstance(frame[1], str))
+    frames = [frame] if single else list(frame)
+    if not 1 <= len(frames) <= MAX_JAC_POINTS:
+        raise ValueError(f"jac_local takes 1..{MAX_JAC_POINTS} frames, not {len(frames)}")
+    off = np.zeros((len(frames), 3)) if offset is None else np.broadcast_to(
+        np.asarray(offset.cpu() if torch.is_tensor(offset) else offset, np.float64), (len(frames), 3))
+    bodies, local = [], np.zeros((len(frames), 3))
+    for k, f in enumerate(frames):
+        objtype, i, body = scan_frame(sys, f)
+        if objtype == abi.SENSOR_OBJ["site"]:
+            if not 0 <= i < sys.m.nsite:
+                raise ValueError(f"site id {i} outside 0..{sys.m.nsite - 1}")
+            local[k] = np.asarray(sys.m.arrays["site_pos"][i]) + np.asarray(mjcf.quat2mat(np.asarray(sys.m.arrays["site_quat"][i], np.float64))).reshape(3, 3) @ off[k]
+        else:
+            local[k] = off[k]
+        if not 0 <= body < sys.nbody:
+            raise ValueError(f"body id {body} outside 0..{sys.nbody - 1}")
+        bodies.append(body)
+    return bodies, np.float32(local)
+
+
+def _jac_out(d: Data, npoint: int, nv: int, out, masked: bool, with_xpnt: bool):
+    shapes = ((d.nenv, npoint, 3, nv), (d.nenv, npoint, 3, nv), (d.nenv, npoint, 3))
+    if out is None:
+        new = torch.zeros if masked else torch.empty
+        out = tuple(new(s, dtype=torch.float32, device=d.device) for s in shapes[:3 if with_xpnt else 2])
+    out = (tuple(out) + (None, None, None))[:3]
+    if out[0] is None and out[1] is None:
+        raise MjlError("jac needs jacp or jacr")
+    for t, s, what in zip(out, shapes, ("jacp", "jacr", "xpnt")):
+        if t is not None and (tuple(t.shape) != s or t.device != d.device):
+            raise MjlError(f"{what} must have shape {s} on {d.device}")
+    return out
+
+
+def jac(sys: Model, d: Data, point, body, mask: Optional[torch.Tensor] = None, out=None):
+    """mjx's support.jac / mj_jac with a leading env axis: (jacp, jacr), [nenv, npoint, 3, nv] each, of the world
+    points `point` [nenv, npoint, 3] ([nenv, 3] with one body) carried by `body` (an id, a name, or a list of
+    npoint of either; checked on the host, ValueError). jacp qvel is the point's world velocity, jacr qvel the
+    body's angular velocity. Poses come from the batch's current qpos inside the call: no forward is needed first.
+    Rows of envs with mask <= 0.5 keep what `out` held (fresh tensors are zeros under a mask). out: (jacp, jacr)
+    to write into, either may be None (then it is not computed and None comes back for it). One launch,
+    capturable when point and out are device tensors. See include/mjx355.h mjl_jac."""
+    ids = _jac_bodies(sys, body)
+    p = torch.as_tensor(point, dtype=torch.float32).to(d.device)
+    if p.dim() == 2:
+        p = p.unsqueeze(1)
+    if tuple(p.shape) != (d.nenv, len(ids), 3):
+        raise MjlError(f"point must have shape {(d.nenv, len(ids), 3)}")
+    jp, jr, _ = _jac_out(d, len(ids), sys.nv, out, mask is not None, False)
+    mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
+    bt = torch.tensor(ids, dtype=torch.int32, device=d.device)
+    check(lib().mjl_jac(d.handle, _ptr(mk), len(ids), _iptr(bt), abi.JAC_FRAME["world"], _ptr(p.contiguous()),
+                        _ptr(jp), _ptr(jr), None, _stream()))
+    return jp, jr
+
+
+def jac_local(sys: Model, d: Data, frame, offset=None, mask: Optional[torch.Tensor] = None, out=None, _dev=None):
+    """Jacobians of points fixed in body or site frames: (jacp, jacr, xpnt), [nenv, npoint, 3, nv] twice and the
+    world points [nenv, npoint, 3]. frame: a body or site (a name, bodies first, or an ("xbody" | "site", id)
+    pair, as ray_scan's frame) or a list of npoint of them; offset ([3] or [npoint, 3], in that frame) moves the
+    point off the frame's origin. The other arguments are `jac`'s; out: (jacp, jacr, xpnt), any may be None but
+    not both Jacobians. One launch. See include/mjx355.h mjl_jac (MJL_JAC_LOCAL)."""
+    if _dev is None:
+        bodies, local = jac_frames(sys, frame, offset)
+        _dev = (torch.tensor(bodies, dtype=torch.int32, device=d.device), torch.tensor(local, device=d.device))
+    bt, lt = _dev
+    n = bt.shape[0]
+    jp, jr, xp = _jac_out(d, n, sys.nv, out, mask is not None, True)
+    mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
+    check(lib().mjl_jac(d.handle, _ptr(mk), n, _iptr(bt), abi.JAC_FRAME["local"], _ptr(lt), _ptr(jp), _ptr(jr),
+                        _ptr(xp), _stream()))
+    return jp, jr, xp
+
+
+def _mass_matrix(sys: Model, d: Data, mask, full, vec, mul, solve):
+    mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
+    nvec = 0 if vec is None else vec.shape[1]
+    check(lib().mjl_mass_matrix(d.handle, _ptr(mk), _ptr(full), nvec, _ptr(vec), _ptr(mul), _ptr(solve), _stream()))
+
+
+def _vec_arg(sys: Model, d: Data, vec, out, masked: bool):
+    """(vec as [nenv, nvec, nv], the result tensor viewed the same way, the result in the caller's shape)"""
+    v = torch.as_tensor(vec, dtype=torch.float32).to(d.device)
+    if v.dim() not in (2, 3) or v.shape[0] != d.nenv or v.shape[-1] != sys.nv:
+        raise MjlError(f"vec must be [{d.nenv}, {sys.nv}] or [{d.nenv}, nvec, {sys.nv}]")
+    v3 = v.reshape(d.nenv, -1, sys.nv).contiguous()
+    if not 1 <= v3.shape[1] <= 64:
+        raise MjlError(f"nvec must be in 1..64, not {v3.shape[1]}")
+    if out is None:
+        out = (torch.zeros if masked else torch.empty)(tuple(v.shape), dtype=torch.float32, device=d.device)
+    elif tuple(out.shape) != tuple(v.shape) or out.device != d.device:
+        raise MjlError(f"out must have shape {tuple(v.shape)} on {d.device}")
+    _ptr(out)
+    return v3, out.view(d.nenv, -1, sys.nv), out
+
+
+def full_m(sys: Model, d: Data, mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mjx's support.full_m with a leading env axis: the dense joint-space inertia [nenv, nv, nv] of the current
+    qpos (composite rigid bodies plus dof_armature; the env's own masses, inertias and armatures while per-env
+    model parameters are on), symmetric bit for bit. No forward is needed first. Rows of envs with mask <= 0.5
+    keep what `out` held (a fresh tensor is zeros under a mask). One launch, capturable. See include/mjx355.h
+    mjl_mass_matrix."""
+    shape = (d.nenv, sys.nv, sys.nv)
+    if out is None:
+        out = (torch.empty if mask is None else torch.zeros)(shape, dtype=torch.float32, device=d.device)
+    elif tuple(out.shape) != shape or out.device != d.device:
+        raise MjlError(f"out must have shape {shape} on {d.device}")
+    _mass_matrix(sys, d, mask, out, None, None, None)
+    return out
+
+
+def mul_m(sys: Model, d: Data, vec, mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mjx's support.mul_m: M vec of the current qpos, vec [nenv, nv] or [nenv, nvec, nv] (nvec <= 64), the result
+    in the same shape. mask / out as full_m. One launch (M is built in the kernel and not stored)."""
+    v3, o3, res = _vec_arg(sys, d, vec, out, mask is not None)
+    _mass_matrix(sys, d, mask, None, v3, o3, None)
+    return res
+
+
+def solve_m(sys: Model, d: Data, vec, mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mjx's smooth.solve_m: M^-1 vec of the current qpos by a Cholesky factor computed in the kernel, vec
+    [nenv, nv] or [nenv, nvec, nv] (nvec <= 64), the result in the same shape. mask / out as full_m. One launch."""
+    v3, o3, res = _vec_arg(sys, d, vec, out, mask is not None)
+    _mass_matrix(sys, d, mask, None, v3, None, o3)
+    return res
+
+
 def step(sys: Model, d: Data, ctrl: Optional[torch.Tensor] = None, nstep: int = 1) -> Data:
     """mjx.step, `nstep` times in one call (mjl_step_n): the same ctrl (None: the stored one) holds for every
     substep, and the state and derived fields are those `nstep` single steps leave. Not differentiated."""
