@@ -400,6 +400,40 @@ int mjl_jac(mjlBatch* batch, const float* mask, int npoint, const int32_t* body,
 int mjl_mass_matrix(mjlBatch* batch, const float* mask, float* full_m, int nvec, const float* vec, float* mul_m,
                     float* solve_m, void* stream);
 
+/* Inverse dynamics of the batch's current state: mj_inverse / mjx.inverse. Given qpos, qvel and an acceleration,
+ * the generalized force that produces it, with limits and contacts. Buffers (float32, device, read at execution
+ * time): qacc [nenv, nv], NULL = the batch's stored MJL_FIELD_QACC (as mj_inverse reads d->qacc); qfrc_inverse
+ * [nenv, nv], required; qfrc_constraint [nenv, nv] or NULL.
+ *   M, qfrc_bias, qfrc_passive  the position and velocity stages of mjl_forward on the current qpos / qvel
+ *   J, D, aref                  the constraint rows of mjl_forward: joint and tendon limits, frictionless and
+ *                               pyramidal contacts
+ *   a_c                         the acceleration the formulas below use. Without MJL_INV_DISCRETE: qacc. With it,
+ *                               qacc is read as the finite difference (qvel' - qvel) / timestep of a step and
+ *                               a_c = qacc + timestep M^-1 (k o qacc) is the continuous-time acceleration the
+ *                               integrator's linear solve maps to it: k[d] = dof_damping[d], under implicitfast
+ *                               additionally - sum_u gear_u^2 biasprm_u[2] over the general actuators on dof d.
+ *                               k applies under the integrator's own condition (implicitfast, or Euler with
+ *                               eulerdamp, and any damping; implicitfast with some biasprm[2] != 0); when it does
+ *                               not hold, a_c = qacc
+ *   jar = J a_c - aref          efc_force_r = -D_r jar_r where jar_r < 0, else 0 (every row kind is one-sided):
+ *                               the constraint update at a given acceleration, no solver iteration
+ *   qfrc_constraint             J' efc_force
+ *   qfrc_inverse                M a_c + qfrc_bias - qfrc_passive - qfrc_constraint
+ * qfrc_inverse is the total of actuator and applied force the motion needs: after mjl_forward, with qacc NULL,
+ * it equals qfrc_actuator + qfrc_applied + sum_b J_b' xfrc_applied[b] up to the solver's residual. ctrl and the
+ * attached applied forces are not read. While MJL_OPT_PER_ENV_MODEL is on, env e uses its own model block, as
+ * mjl_forward does.
+ * Read: qpos, qvel, the model, qacc (or the stored one). Written: the outputs, nothing else of the batch: the
+ * state, qacc_warmstart and every stored derived field (xpos, qfrc_*, sensordata, stats) stay bit for bit. The
+ * constraint rows live in the launch's on-chip memory; when they overflow it, or with MJL_OPT_FORCE_GLOBAL_ROWS,
+ * in the batch's per-env row scratch, which the call then overwrites. No entry reads that scratch across calls
+ * (mjl_forward_contacts, mjl_sensors and mjl_body_data fill it and read it within one call, in stream order).
+ * Envs with mask <= 0.5 keep their rows (mask NULL = all envs). One launch, no solver, no sensors; no allocation,
+ * no synchronisation, capturable. MJL_ERR_ARG: a null batch; qfrc_inverse NULL; unknown flag bits. */
+enum { MJL_INV_DISCRETE = 1 };
+int mjl_inverse(mjlBatch* batch, const float* mask, const float* qacc, int flags, float* qfrc_inverse,
+                float* qfrc_constraint, void* stream);
+
 /* Ray casts against the batch's current state: mjx.ray / mj_ray (mjl_ray, caller-chosen world rays per env) and
  * ray patterns carried by a body or site frame (mjl_ray_scan: height scanner, lidar fan, rangefinder).
  * Buffers (float32 / int32, device): mjl_ray pnt, vec [nenv, nray, 3] in the world frame; mjl_ray_scan lpnt, lvec

@@ -24,6 +24,7 @@
 #include "sensor_kernels.hip"
 #include "body_kernels.hip"
 #include "dyn_kernels.hip"
+#include "inverse_kernels.hip"
 #include "ray_kernels.hip"
 #include "model_host.h"
 
@@ -671,6 +672,27 @@ int mjl_mass_matrix(mjlBatch* B, const float* mask, float* full_m, int nvec, con
   A.m = B->d_model; A.m_env = B->d_model_env; A.qpos = B->s.qpos; A.mask = mask;
   A.nenv = B->nenv; A.nvec = nvec; A.vec = vec; A.full_m = full_m; A.mul_m = mul_m; A.solve_m = solve_m;
   hipLaunchKernelGGL(mass_matrix_kernel, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
+}
+
+// One launch (inverse_kernels.hip): the forward pass's smooth phases and rows, no solver, nothing of the batch written.
+int mjl_inverse(mjlBatch* B, const float* mask, const float* qacc, int flags, float* qfrc_inverse,
+                float* qfrc_constraint, void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (!qfrc_inverse) return fail(MJL_ERR_ARG, "mjl_inverse: qfrc_inverse is required");
+  if (flags & ~MJL_INV_DISCRETE) return fail(MJL_ERR_ARG, "mjl_inverse: flags = %d: 0 or MJL_INV_DISCRETE", flags);
+  HIPCHK(hipSetDevice(B->device));
+  InvArgs A;
+  A.m = B->d_model; A.m_env = B->d_model_env; A.qpos = B->s.qpos; A.qvel = B->s.qvel;
+  A.qacc = qacc ? qacc : B->s.qacc; A.mask = mask;
+  A.qfrc_inverse = qfrc_inverse; A.qfrc_constraint = qfrc_constraint;
+  A.scratch = B->d_scratch; A.scratch_stride = B->scratch_stride; A.gmax_efc = B->gmax_efc; A.gmax_con = B->gmax_con;
+  A.nenv = B->nenv; A.flags = flags; A.force_global_rows = B->force_global_rows;
+  if (B->model->nvc == 0)
+    hipLaunchKernelGGL(inverse_kernel<DHum>, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
+  else
+    hipLaunchKernelGGL(inverse_kernel<DGen>, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
   HIPCHK(hipGetLastError());
   return MJL_OK;
 }

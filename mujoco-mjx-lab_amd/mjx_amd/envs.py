@@ -175,6 +175,17 @@ class HumanoidEnv:
             self._full_m = torch.zeros((self.num_envs, self.sys.nv, self.sys.nv), device=self.obs.device)
         return full_m(self.sys, self.data, mask, self._full_m)
 
+    def inverse(self, qacc=None, discrete: bool = False, mask: Optional[torch.Tensor] = None):
+        """Inverse dynamics of the envs' current state (mjx.inverse): (qfrc_inverse, qfrc_constraint), each
+        [num_envs, nv], in tensors this env owns (zeros at first, written again by every call). qacc None: the
+        stored qacc of the last forward; a tensor is read at execution time, so a captured call sees what it
+        holds at each replay. One launch that writes nothing of the envs' state, capturable with the step."""
+        from .mjx import inverse
+        if getattr(self, "_inverse", None) is None:
+            self._inverse = (torch.zeros((self.num_envs, self.sys.nv), device=self.obs.device),
+                             torch.zeros((self.num_envs, self.sys.nv), device=self.obs.device))
+        return inverse(self.sys, self.data, qacc, discrete, mask, self._inverse, with_constraint=True)
+
     def scan(self, frame, pattern, align: str = "pose", flg_static: bool = True, bodyexclude="self",
              cutoff: float = 0.0, mask: Optional[torch.Tensor] = None):
         """Range scan of the envs' current state (mjx.ray_scan): `pattern` = (lpnt, lvec) [nray, 3] in the frame

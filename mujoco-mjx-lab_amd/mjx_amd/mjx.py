@@ -617,6 +617,35 @@ def solve_m(sys: Model, d: Data, vec, mask: Optional[torch.Tensor] = None, out: 
     return res
 
 
+def inverse(sys: Model, d: Data, qacc=None, discrete: bool = False, mask: Optional[torch.Tensor] = None, out=None,
+            with_constraint: bool = False):
+    """mjx.inverse with a leading env axis: qfrc_inverse [nenv, nv], the generalized force that gives the current
+    qpos / qvel the acceleration `qacc` ([nenv, nv]; None: the stored qacc of the last forward), limits and
+    contacts included: M a + qfrc_bias - qfrc_passive - qfrc_constraint with the constraint force evaluated at a,
+    no solver. discrete: `qacc` is a step's (qvel' - qvel) / timestep and is first mapped back through the
+    integrator's damping solve. with_constraint: (qfrc_inverse, qfrc_constraint) come back. out: the tensor, or
+    with_constraint the pair of tensors, to write into. ctrl and applied forces take no part (the result is their
+    total); per-env model parameters do. Rows of envs with mask <= 0.5 keep what `out` held (a fresh tensor is
+    zeros under a mask). Nothing of `d` is written. One launch, capturable. See include/mjx355.h mjl_inverse."""
+    shape = (d.nenv, sys.nv)
+    if qacc is not None:
+        qacc = torch.as_tensor(qacc, dtype=torch.float32).to(d.device).contiguous()
+        if tuple(qacc.shape) != shape:
+            raise MjlError(f"qacc must have shape {shape}")
+    outs = list(out) if isinstance(out, (tuple, list)) else [out, None]
+    if len(outs) != 2 or (outs[1] is not None and not with_constraint):
+        raise MjlError("out is one tensor, or (qfrc_inverse, qfrc_constraint) with with_constraint")
+    for i in range(2 if with_constraint else 1):
+        if outs[i] is None:
+            outs[i] = (torch.empty if mask is None else torch.zeros)(shape, dtype=torch.float32, device=d.device)
+        elif tuple(outs[i].shape) != shape or outs[i].device != d.device:
+            raise MjlError(f"out must have shape {shape} on {d.device}")
+    mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
+    flags = abi.INV_DISCRETE if discrete else 0
+    check(lib().mjl_inverse(d.handle, _ptr(mk), _ptr(qacc), flags, _ptr(outs[0]), _ptr(outs[1]), _stream()))
+    return (outs[0], outs[1]) if with_constraint else outs[0]
+
+
 def step(sys: Model, d: Data, ctrl: Optional[torch.Tensor] = None, nstep: int = 1) -> Data:
     """mjx.step, `nstep` times in one call (mjl_step_n): the same ctrl (None: the stored one) holds for every
     substep, and the state and derived fields are those `nstep` single steps leave. Not differentiated."""
