@@ -400,6 +400,56 @@ int mjl_jac(mjlBatch* batch, const float* mask, int npoint, const int32_t* body,
 int mjl_mass_matrix(mjlBatch* batch, const float* mask, float* full_m, int nvec, const float* vec, float* mul_m,
                     float* solve_m, void* stream);
 
+/* Time derivatives of mjl_jac's point Jacobians and the velocity-product term of a task acceleration
+ * (xdd = J qacc + Jdot qvel): mj_jacDot for npoint points per env. npoint, body, frame (MJL_JAC_WORLD /
+ * MJL_JAC_LOCAL) and pnt are exactly mjl_jac's; a MJL_JAC_WORLD point is attached to its body at this instant.
+ * Buffers (float32, device): jacp_dot, jacr_dot [nenv, npoint, 3, nv] row-major; jdotv [nenv, npoint, 6] =
+ * (jacp_dot qvel ; jacr_dot qvel), the point's classical acceleration and the body's angular acceleration at
+ * qacc = 0. Any output may be NULL, not all three; jdotv alone is the cheap call (no nv-wide stores).
+ * The outputs are the derivatives of mjl_jac's outputs along the motion qpos(t) whose rate is the batch's qvel
+ * (positions integrate as the step integrates them, the free joint's angular rates body-local), the point fixed
+ * in its body. With a_d, p_d the world axis and anchor of dof d as mjl_jac defines them, x the point and
+ * xd = jacp qvel its velocity, column d is zero unless dof d moves the body, and for such a dof:
+ *   hinge                      ad = w x a_d, pd = v(p_d): w and v(.) the angular velocity and the velocity field
+ *                              of the dofs that precede d on its chain (earlier hinges of the same body, every
+ *                              dof of the ancestor bodies; including d itself changes nothing)
+ *   free joint, translation i  both columns are zero
+ *   free joint, rotation i     ad = (R_b qvel_rot) x (R_b e_i): the axis turns with the body's whole angular
+ *                              velocity; pd = qvel_lin
+ *   in every moving case       jacr_dot[:, d] = ad      jacp_dot[:, d] = ad x (x - p_d) + a_d x (xd - pd)
+ * jdotv is the product of these columns with qvel, summed in the kernel. With qvel = 0 every output is exactly
+ * zero. Body 0 gives zero rows; a body id outside 0..nbody-1 gives NaN rows (mjl_jac's rule).
+ * Poses and rates: forward kinematics of the batch's current qpos / qvel, run in the same launch; nothing of the
+ * batch is read but qpos and qvel, nothing written, so the call is correct right after mjl_env_step. Per-env
+ * model parameters and applied forces do not matter (no geometric field is per-env).
+ * Envs with mask <= 0.5 keep their rows (mask NULL = all envs). One launch, no allocation, no synchronisation,
+ * capturable. MJL_ERR_ARG: a null batch or body; all three outputs NULL; npoint outside 1..256; an unknown frame;
+ * pnt NULL with MJL_JAC_WORLD. */
+int mjl_jac_dot(mjlBatch* batch, const float* mask, int npoint, const int32_t* body, int frame, const float* pnt,
+                float* jacp_dot, float* jacr_dot, float* jdotv, void* stream);
+
+/* Centroidal quantities of nsub subtrees per env: the Jacobian of the subtree's centre of mass
+ * (mj_jacSubtreeCom), the angular-momentum matrix about that centre (mj_angmomMat) and their bias. Buffers
+ * (float32 / int32, device, read at execution time): body [nsub], nsub in 1..32, the subtree roots, shared by all
+ * envs, 0 = the whole model; jac_com, angmom_mat [nenv, nsub, 3, nv] row-major; bias [nenv, nsub, 6]. Any output
+ * may be NULL, not all three. With S(b) = [b, body_subtree_end[b]), m_b = sum_k m_k over S(b), c_b =
+ * subtree_com[b], and jacp_k / jacr_k mjl_jac's Jacobians of body k at xipos_k:
+ *   jac_com[b]     sum_k m_k jacp_k / m_b
+ *   angmom_mat[b]  sum_k [ I_k jacr_k + m_k (xipos_k - c_b) x jacp_k ], I_k the world inertia as mjl_body_data
+ *                  defines it: the angular momentum about the subtree's own centre of mass
+ *   bias[b]        ( d/dt(jac_com) qvel ; d/dt(angmom_mat) qvel ) = ( sum_k m_k a_k / m_b ; sum_k [ I_k dw_k +
+ *                  w_k x I_k w_k + m_k (xipos_k - c_b) x a_k ] ): the acceleration of the centre of mass and the
+ *                  rate of the angular momentum at qacc = 0 (a_k, dw_k: the velocity-product accelerations)
+ * so jac_com qvel = subtree_linvel[b] and angmom_mat qvel = subtree_angmom[b] of mjl_body_data. A massless
+ * subtree gives zero rows; a body id outside 0..nbody-1 gives NaN rows.
+ * Poses and rates as mjl_jac_dot: from the batch's current qpos / qvel in the same launch, nothing written. While
+ * MJL_OPT_PER_ENV_MODEL is on, env e uses its own block's body_mass, body_inertia and body_ipos, as
+ * mjl_mass_matrix does.
+ * Envs with mask <= 0.5 keep their rows (mask NULL = all envs). One launch, no allocation, no synchronisation,
+ * capturable. MJL_ERR_ARG: a null batch or body; nsub outside 1..32; every output NULL. */
+int mjl_centroidal(mjlBatch* batch, const float* mask, int nsub, const int32_t* body, float* jac_com,
+                   float* angmom_mat, float* bias, void* stream);
+
 /* Inverse dynamics of the batch's current state: mj_inverse / mjx.inverse. Given qpos, qvel and an acceleration,
  * the generalized force that produces it, with limits and contacts. Buffers (float32, device, read at execution
  * time): qacc [nenv, nv], NULL = the batch's stored MJL_FIELD_QACC (as mj_inverse reads d->qacc); qfrc_inverse

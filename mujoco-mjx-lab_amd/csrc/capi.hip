@@ -24,6 +24,7 @@
 #include "sensor_kernels.hip"
 #include "body_kernels.hip"
 #include "dyn_kernels.hip"
+#include "taskspace_kernels.hip"
 #include "inverse_kernels.hip"
 #include "ray_kernels.hip"
 #include "model_host.h"
@@ -672,6 +673,43 @@ int mjl_mass_matrix(mjlBatch* B, const float* mask, float* full_m, int nvec, con
   A.m = B->d_model; A.m_env = B->d_model_env; A.qpos = B->s.qpos; A.mask = mask;
   A.nenv = B->nenv; A.nvec = nvec; A.vec = vec; A.full_m = full_m; A.mul_m = mul_m; A.solve_m = solve_m;
   hipLaunchKernelGGL(mass_matrix_kernel, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
+}
+
+// One launch each (taskspace_kernels.hip): kinematics and rates of the current qpos / qvel inside the kernel,
+// nothing of the batch written.
+int mjl_jac_dot(mjlBatch* B, const float* mask, int npoint, const int32_t* body, int frame, const float* pnt,
+                float* jacp_dot, float* jacr_dot, float* jdotv, void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (!body) return fail(MJL_ERR_ARG, "mjl_jac_dot: body is required");
+  if (!jacp_dot && !jacr_dot && !jdotv) return fail(MJL_ERR_ARG, "mjl_jac_dot: every output is NULL");
+  if (npoint < 1 || npoint > 256) return fail(MJL_ERR_ARG, "mjl_jac_dot: npoint = %d outside 1..256", npoint);
+  if (frame != MJL_JAC_WORLD && frame != MJL_JAC_LOCAL)
+    return fail(MJL_ERR_ARG, "mjl_jac_dot: frame = %d: MJL_JAC_WORLD or MJL_JAC_LOCAL", frame);
+  if (frame == MJL_JAC_WORLD && !pnt) return fail(MJL_ERR_ARG, "mjl_jac_dot: pnt is required with MJL_JAC_WORLD");
+  HIPCHK(hipSetDevice(B->device));
+  JacDotArgs A;
+  A.m = B->d_model; A.tab = B->d_dyntab; A.qpos = B->s.qpos; A.qvel = B->s.qvel; A.mask = mask;
+  A.nenv = B->nenv; A.npoint = npoint; A.frame = frame; A.body = body; A.pnt = pnt;
+  A.jacp_dot = jacp_dot; A.jacr_dot = jacr_dot; A.jdotv = jdotv;
+  hipLaunchKernelGGL(jac_dot_kernel, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
+}
+
+int mjl_centroidal(mjlBatch* B, const float* mask, int nsub, const int32_t* body, float* jac_com, float* angmom_mat,
+                   float* bias, void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (!body) return fail(MJL_ERR_ARG, "mjl_centroidal: body is required");
+  if (!jac_com && !angmom_mat && !bias) return fail(MJL_ERR_ARG, "mjl_centroidal: every output is NULL");
+  if (nsub < 1 || nsub > 32) return fail(MJL_ERR_ARG, "mjl_centroidal: nsub = %d outside 1..32", nsub);
+  HIPCHK(hipSetDevice(B->device));
+  CentArgs A;
+  A.m = B->d_model; A.m_env = B->d_model_env; A.tab = B->d_dyntab; A.qpos = B->s.qpos; A.qvel = B->s.qvel;
+  A.mask = mask; A.nenv = B->nenv; A.nsub = nsub; A.body = body;
+  A.jac_com = jac_com; A.angmom_mat = angmom_mat; A.bias = bias;
+  hipLaunchKernelGGL(centroidal_kernel, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
   HIPCHK(hipGetLastError());
   return MJL_OK;
 }

@@ -166,6 +166,39 @@ class HumanoidEnv:
         tabs, out = bufs[key]
         return jac_local(self.sys, self.data, frames, offset, mask, out, _dev=tabs)
 
+    def jac_dot(self, frames, offset=None, mask: Optional[torch.Tensor] = None):
+        """Time derivatives of jac()'s Jacobians and the velocity-product term (mjx.jac_dot_local): (jacp_dot,
+        jacr_dot, jdotv) in tensors this env owns, allocated (zeros) at the first call with these (frames,
+        offset) and written again by every later one: after one eager call it is one launch on the post-step
+        state that can be captured with the step, as jac()."""
+        from .mjx import jac_dot_local, jac_frames
+        bodies, local = jac_frames(self.sys, frames, offset)
+        key = (tuple(bodies), local.tobytes())
+        bufs = self.__dict__.setdefault("_jac_dot_bufs", {})
+        if key not in bufs:
+            dev, n, p, nv = self.obs.device, self.num_envs, len(bodies), self.sys.nv
+            bufs[key] = ((torch.tensor(bodies, dtype=torch.int32, device=dev), torch.tensor(local, device=dev)),
+                         (torch.zeros((n, p, 3, nv), device=dev), torch.zeros((n, p, 3, nv), device=dev),
+                          torch.zeros((n, p, 6), device=dev)))
+        tabs, out = bufs[key]
+        return jac_dot_local(self.sys, self.data, frames, offset, mask, out, _dev=tabs)
+
+    def centroidal(self, body=0, mask: Optional[torch.Tensor] = None):
+        """Centroidal quantities of the subtrees rooted at `body` (mjx.centroidal; 0: the whole model): (jac_com,
+        angmom_mat, bias) in tensors this env owns, allocated (zeros) with the roots' device table at the first
+        call with these roots and written again by every later one: one launch on the post-step state,
+        capturable with the step."""
+        from .mjx import _subtree_roots, centroidal
+        roots = tuple(_subtree_roots(self.sys, body))
+        bufs = self.__dict__.setdefault("_centroidal_bufs", {})
+        if roots not in bufs:
+            dev, n, s, nv = self.obs.device, self.num_envs, len(roots), self.sys.nv
+            bufs[roots] = (torch.tensor(roots, dtype=torch.int32, device=dev),
+                           (torch.zeros((n, s, 3, nv), device=dev), torch.zeros((n, s, 3, nv), device=dev),
+                            torch.zeros((n, s, 6), device=dev)))
+        tab, out = bufs[roots]
+        return centroidal(self.sys, self.data, body, mask, out, _dev=tab)
+
     def full_m(self, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The joint-space inertia [num_envs, nv, nv] of the envs' current state (mjx.full_m) in a tensor this env
         owns (zeros at first, written again by every call): one launch on the post-step state, capturable with

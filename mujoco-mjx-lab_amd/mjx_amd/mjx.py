@@ -564,6 +564,130 @@ def jac_local(sys: Model, d: Data, frame, offset=None, mask: Optional[torch.Tens
     return jp, jr, xp
 
 
+def _jac_dot_out(d: Data, npoint: int, nv: int, out, masked: bool):
+    shapes = ((d.nenv, npoint, 3, nv), (d.nenv, npoint, 3, nv), (d.nenv, npoint, 6))
+    if out is None:
+        new = torch.zeros if masked else torch.empty
+        out = tuple(new(s, dtype=torch.float32, device=d.device) for s in shapes)
+    out = (tuple(out) + (None, None, None))[:3]
+    if all(t is None for t in out):
+        raise MjlError("jac_dot needs jacp_dot, jacr_dot or jdotv")
+    for t, s, what in zip(out, shapes, ("jacp_dot", "jacr_dot", "jdotv")):
+        if t is not None and (tuple(t.shape) != s or t.device != d.device):
+            raise MjlError(f"{what} must have shape {s} on {d.device}")
+    return out
+
+
+def jac_dot(sys: Model, d: Data, point, body, mask: Optional[torch.Tensor] = None, out=None):
+    """mj_jacDot with a leading env axis: (jacp_dot, jacr_dot, jdotv), the time derivatives [nenv, npoint, 3, nv]
+    of `jac`'s Jacobians along the batch's current qvel, and jdotv [nenv, npoint, 6] = (jacp_dot qvel ; jacr_dot
+    qvel), the velocity-product term of the task acceleration J qacc + Jdot qvel. point / body / mask as `jac`;
+    a world point is attached to its body at this instant. out: (jacp_dot, jacr_dot, jdotv) to write into, any may
+    be None but not all (then it is not computed and None comes back for it): (None, None, jdotv) is the cheap
+    call. With qvel = 0 everything is exactly zero. One launch, capturable when point and out are device
+    tensors. See include/mjx355.h mjl_jac_dot."""
+    ids = _jac_bodies(sys, body)
+    p = torch.as_tensor(point, dtype=torch.float32).to(d.device)
+    if p.dim() == 2:
+        p = p.unsqueeze(1)
+    if tuple(p.shape) != (d.nenv, len(ids), 3):
+        raise MjlError(f"point must have shape {(d.nenv, len(ids), 3)}")
+    jp, jr, jv = _jac_dot_out(d, len(ids), sys.nv, out, mask is not None)
+    mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
+    bt = torch.tensor(ids, dtype=torch.int32, device=d.device)
+    check(lib().mjl_jac_dot(d.handle, _ptr(mk), len(ids), _iptr(bt), abi.JAC_FRAME["world"], _ptr(p.contiguous()),
+                            _ptr(jp), _ptr(jr), _ptr(jv), _stream()))
+    return jp, jr, jv
+
+
+def jac_dot_local(sys: Model, d: Data, frame, offset=None, mask: Optional[torch.Tensor] = None, out=None, _dev=None):
+    """`jac_dot` of points fixed in body or site frames: (jacp_dot, jacr_dot, jdotv) of `jac_local`'s points
+    (frame / offset as there). One launch. See include/mjx355.h mjl_jac_dot (MJL_JAC_LOCAL)."""
+    if _dev is None:
+        bodies, local = jac_frames(sys, frame, offset)
+        _dev = (torch.tensor(bodies, dtype=torch.int32, device=d.device), torch.tensor(local, device=d.device))
+    bt, lt = _dev
+    n = bt.shape[0]
+    jp, jr, jv = _jac_dot_out(d, n, sys.nv, out, mask is not None)
+    mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
+    check(lib().mjl_jac_dot(d.handle, _ptr(mk), n, _iptr(bt), abi.JAC_FRAME["local"], _ptr(lt), _ptr(jp), _ptr(jr),
+                            _ptr(jv), _stream()))
+    return jp, jr, jv
+
+
+MAX_SUBTREES = 32  # mjl_centroidal's nsub
+
+
+def _subtree_roots(sys: Model, body) -> list:
+    """Body ids of the subtree roots `body` (an id, a name, or a list of either; 0: the whole model)."""
+    ids = []
+    for b in _as_list(body):
+        if isinstance(b, str):
+            i = sys.m.name2id("body", b)
+            if i < 0:
+                raise ValueError(f"no body named {b!r}")
+        else:
+            i = int(b)
+        if not 0 <= i < sys.nbody:
+            raise ValueError(f"body id {i} outside 0..{sys.nbody - 1}")
+        ids.append(i)
+    if not 1 <= len(ids) <= MAX_SUBTREES:
+        raise ValueError(f"centroidal takes 1..{MAX_SUBTREES} subtrees, not {len(ids)}")
+    return ids
+
+
+def centroidal(sys: Model, d: Data, body=0, mask: Optional[torch.Tensor] = None, out=None, _dev=None):
+    """The centroidal quantities of the subtrees rooted at `body` (an id, a name, or a list of up to 32 of
+    either; 0: the whole model): (jac_com, angmom_mat, bias). jac_com [nenv, nsub, 3, nv] is mj_jacSubtreeCom
+    (jac_com qvel = subtree_linvel), angmom_mat [nenv, nsub, 3, nv] mj_angmomMat, the angular momentum about the
+    subtree's own centre of mass (angmom_mat qvel = subtree_angmom), and bias [nenv, nsub, 6] their derivatives
+    applied to qvel: the centre of mass's acceleration and the angular momentum's rate at qacc = 0. Masses and
+    inertias are the env's own while per-env model parameters are on. out: (jac_com, angmom_mat, bias) to write
+    into, any may be None but not all (then it is not computed and None comes back for it). Rows of envs with
+    mask <= 0.5 keep what `out` held (fresh tensors are zeros under a mask). Nothing of `d` is written. One
+    launch, capturable when out holds device tensors. See include/mjx355.h mjl_centroidal."""
+    if _dev is None:
+        _dev = torch.tensor(_subtree_roots(sys, body), dtype=torch.int32, device=d.device)
+    n = _dev.shape[0]
+    shapes = ((d.nenv, n, 3, sys.nv), (d.nenv, n, 3, sys.nv), (d.nenv, n, 6))
+    if out is None:
+        new = torch.empty if mask is None else torch.zeros
+        out = tuple(new(s, dtype=torch.float32, device=d.device) for s in shapes)
+    out = (tuple(out) + (None, None, None))[:3]
+    if all(t is None for t in out):
+        raise MjlError("centroidal needs jac_com, angmom_mat or bias")
+    for t, s, what in zip(out, shapes, ("jac_com", "angmom_mat", "bias")):
+        if t is not None and (tuple(t.shape) != s or t.device != d.device):
+            raise MjlError(f"{what} must have shape {s} on {d.device}")
+    mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
+    check(lib().mjl_centroidal(d.handle, _ptr(mk), n, _iptr(_dev), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()))
+    return out
+
+
+def _centroidal_one(sys: Model, d: Data, body, mask, out, which: int):
+    n = len(_subtree_roots(sys, body))
+    shape = (d.nenv, n, 3, sys.nv)
+    if out is None:
+        out = (torch.empty if mask is None else torch.zeros)(shape, dtype=torch.float32, device=d.device)
+    outs = [None, None, None]
+    outs[which] = out
+    return centroidal(sys, d, body, mask, tuple(outs))[which]
+
+
+def jac_subtree_com(sys: Model, d: Data, body=0, mask: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mj_jacSubtreeCom with a leading env axis: [nenv, nsub, 3, nv], the Jacobian of the centre of mass of the
+    subtrees rooted at `body` (`centroidal`'s first output alone). mask / out as there."""
+    return _centroidal_one(sys, d, body, mask, out, 0)
+
+
+def angmom_mat(sys: Model, d: Data, body=0, mask: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mj_angmomMat with a leading env axis: [nenv, nsub, 3, nv], the angular-momentum matrix of the subtrees
+    rooted at `body` about their own centres of mass (`centroidal`'s second output alone). mask / out as there."""
+    return _centroidal_one(sys, d, body, mask, out, 1)
+
+
 def _mass_matrix(sys: Model, d: Data, mask, full, vec, mul, solve):
     mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
     nvec = 0 if vec is None else vec.shape[1]
