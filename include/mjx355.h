@@ -111,7 +111,7 @@ typedef struct mjlModelDesc {
    * integrator's matrix gets -dt * gear^2 * biasprm[2] on dof d's diagonal, whether or not the force was
    * clipped (derivative.deriv_smooth_vel). actuator_kind: MJL_ACT_MOTOR (0) reads none of the four fields
    * below (gain 1, no bias, no force limit), so an all-zero group is the torque motor; MJL_ACT_GENERAL reads
-   * them all. Not differentiated: see the step VJP entries. */
+   * them all. Not differentiated: see the step VJP entries and mjl_step_jacobian. */
   int32_t actuator_kind[MJL_MAXU], actuator_forcelimited[MJL_MAXU];
   double actuator_gain[MJL_MAXU], actuator_biasprm[MJL_MAXU][3], actuator_forcerange[MJL_MAXU][2];
 
@@ -221,9 +221,12 @@ int mjl_batch_nenv(const mjlBatch* batch);
  * model's values (nenv x 46976 bytes, the size of one device model block: 96 MB for 2048 envs; call
  * outside stream capture; 0 frees them). See mjl_batch_set_model_params.
  * MJL_OPT_RAY_CHUNK (default 0, tuning hook of tools/ray_bench.py): value = rays per wavefront of mjl_ray /
- * mjl_ray_scan, 0..65535; 0 = the library's choice. The results do not depend on it. */
+ * mjl_ray_scan, 0..65535; 0 = the library's choice. The results do not depend on it.
+ * MJL_OPT_LINEARIZE_GROUPS (default 0, test and tuning hook of tools/linearize_bench.py): value = row groups per
+ * env of mjl_step_jacobian, 0..16; 0 = the library's choice from the env count. The results do not depend on it,
+ * bit for bit. */
 enum { MJL_OPT_STORE_DERIVED = 0, MJL_OPT_FORCE_GLOBAL_ROWS = 1, MJL_OPT_VJP_UNROLLED = 2, MJL_OPT_RESET_POOL = 3,
-       MJL_OPT_VJP_TAPE = 4, MJL_OPT_PER_ENV_MODEL = 5, MJL_OPT_RAY_CHUNK = 6 };
+       MJL_OPT_VJP_TAPE = 4, MJL_OPT_PER_ENV_MODEL = 5, MJL_OPT_RAY_CHUNK = 6, MJL_OPT_LINEARIZE_GROUPS = 7 };
 int mjl_batch_set_option(mjlBatch* batch, int option, int value);
 
 /* Per-env model parameters (domain randomisation; in MJX jax.vmap(step, in_axes=(model_axes, 0)) over a
@@ -252,8 +255,8 @@ int mjl_batch_set_option(mjlBatch* batch, int option, int value);
  * While the option is on, mjl_forward, mjl_forward_contacts, mjl_step, mjl_env_step (its in-kernel
  * auto-reset and pooled resets included), mjl_env_reset and mjl_env_fill_reset_pool run env e on its block;
  * pooled resets are computed with the blocks as they are at the fill. mjl_speedtest_step runs the model's
- * own values. Not differentiated: every step VJP, record and replay entry returns MJL_ERR_UNSUPPORTED
- * while the option is on. The renderer is not concerned (no geometric field). */
+ * own values. Not differentiated: every step VJP, record and replay entry and mjl_step_jacobian returns
+ * MJL_ERR_UNSUPPORTED while the option is on. The renderer is not concerned (no geometric field). */
 #define MJL_NMP 6
 enum { MJL_MP_BODY_MASS = 0, MJL_MP_BODY_INERTIA = 1, MJL_MP_DOF_DAMPING = 2, MJL_MP_DOF_ARMATURE = 3,
        MJL_MP_ACTUATOR_GEAR = 4, MJL_MP_PAIR_FRICTION = 5 };
@@ -618,7 +621,8 @@ int mjl_env_set_reset_keys(mjlBatch* batch, const uint32_t* dev_keys, int mode);
  * does not clear them. mjl_speedtest_step, mjl_env_reset, the auto-reset inside mjl_env_step and
  * mjl_env_fill_reset_pool start from a fresh make_data and run with zero applied force.
  * Not differentiated: every step VJP, record and replay entry (mjl_step_vjp*, mjl_env_step_vjp*,
- * mjl_env_step_record*, mjl_env_step_vjp_replay*) returns MJL_ERR_UNSUPPORTED while anything is attached.
+ * mjl_env_step_record*, mjl_env_step_vjp_replay*) and mjl_step_jacobian return MJL_ERR_UNSUPPORTED while anything
+ * is attached.
  * A host-side pointer set; MJL_ERR_ARG for a null batch. */
 int mjl_batch_attach_applied(mjlBatch* batch, const float* qfrc_applied, const float* xfrc_applied);
 
@@ -682,6 +686,37 @@ int mjl_env_step_vjp_full(mjlBatch* batch, const float* act, const float* g_qpos
                           const float* g_qacc_ws, const float* g_rew, const float* g_aux, float* out_qpos,
                           float* out_qvel, float* out_qacc_ws, float* out_act, float* out_aux,
                           float* nonfinite_count, void* stream);
+
+/* Linearization of one mjl_step at the batch's current qpos, qvel, qacc_warmstart: the transition matrices
+ * A = dx'/dx and B = dx'/du (mjd_transitionFD; jax.jacobian(mjx.step)). ctrl [nenv, nu] (device, read at execution
+ * time), NULL = the stored ctrl, as mjl_step. Nothing of the batch is written. A or B may be NULL (not both): a NULL
+ * output is not stored, and with A NULL the reverse passes behind ctrl's cotangent are not run.
+ * flags selects the layout:
+ *   MJL_JAC_TANGENT  A [nenv, 2nv, 2nv], B [nenv, 2nv, nu], state x = (dq, qvel) in the tangent space, as
+ *                    mjd_transitionFD. An input dq acts as mj_integratePos(qpos, dq, 1): hinge coordinates and a free
+ *                    joint's position add, its quaternion becomes q (x) exp(d), d a rotation vector in the body
+ *                    frame (linearised: dquat = 1/2 q (x) (0, d)). An output difference is mj_differentiatePos: for
+ *                    the free quaternion the rotation vector of conj(q'0) (x) q' (linearised: d' = 2 vec(conj(q'0)
+ *                    (x) dquat'), q'0 the post-step, normalised quaternion). Both maps are applied in the kernel.
+ *   0                A [nenv, nq+nv, nq+nv], B [nenv, nq+nv, nu] in raw coordinates: row i is the derivative of
+ *                    entry i of (qpos', qvel'), columns (qpos, qvel) and ctrl, as jax.jacobian(mjx.step) lays it out.
+ * The constraint solve is differentiated at its converged active set (the implicit derivative of mjl_step_vjp with
+ * MJL_OPT_VJP_UNROLLED off): row i of [A | B] is what mjl_step_vjp returns for the i-th basis cotangent. This
+ * entry always uses the implicit form, whatever MJL_OPT_VJP_UNROLLED is set to. qacc_warmstart seeds the solver
+ * and has no column.
+ * One launch of one wavefront per (env, row group): the step's forward runs once per wavefront, the reverse passes
+ * once per row, from cotangents formed on chip. The number of row groups per env follows from the env count
+ * (MJL_OPT_LINEARIZE_GROUPS overrides it); the result does not depend on it. Envs with mask <= 0.5 keep their rows
+ * of A and B (mask NULL = all envs).
+ * The per-wavefront scratch (the step VJP's, times the row groups) is allocated by the first call and regrown when a
+ * later call needs more (more row groups): so the first call at a given setting happens outside stream capture, and
+ * a regrow invalidates graphs captured before it. After that: no allocation, no synchronisation, capturable.
+ * MJL_ERR_ARG: a null batch; A and B both NULL; unknown flag bits (checked in this order, before anything else).
+ * MJL_ERR_UNSUPPORTED, with the step VJPs' messages: applied forces attached, MJL_OPT_PER_ENV_MODEL on, or a model
+ * with a non-motor actuator. */
+enum { MJL_JAC_TANGENT = 1 };
+int mjl_step_jacobian(mjlBatch* batch, const float* mask, const float* ctrl, int flags, float* A, float* B,
+                      void* stream);
 
 /* The persistent per-env state (what a step reads and writes: Data.qpos, qvel, qacc_warmstart,
  * time, plus the env aux) as packed rows [nenv, mjl_state_size] = [qpos | qvel | qacc_warmstart |

@@ -26,6 +26,7 @@
 #include "dyn_kernels.hip"
 #include "taskspace_kernels.hip"
 #include "inverse_kernels.hip"
+#include "linearize_kernels.hip"
 #include "ray_kernels.hip"
 #include "model_host.h"
 
@@ -100,6 +101,8 @@ struct mjlBatch {
   float* d_unr;          // unrolled VJP: per env solve tape + row accumulators (allocated on first use)
   TapeDims unr_dims;
   int adj_stride, adj_row_floats;
+  int adj_blocks;        // strides d_adj_scratch holds: nenv, or nenv x row groups once mjl_step_jacobian has run
+  int lin_groups;        // MJL_OPT_LINEARIZE_GROUPS: row groups per env of mjl_step_jacobian, 0 = the host's rule
   const unsigned long long* ctr_base;  // device RNG counter base (mjl_batch_set_counter_base), or null
   int* vjp_exp;       // per-env cotangent exponents of the guarded env-step VJPs (mjl_vjp_scale_attach), or null
   int vjp_exp_thr;    // log2 of the output magnitude from which an env's cotangents are rescaled
@@ -134,6 +137,10 @@ static int launch_model_params(mjlBatch* B, const float* const* values, const fl
   HIPCHK(hipGetLastError());
   return MJL_OK;
 }
+
+// Row groups per env of mjl_step_jacobian (linearize_kernels.hip): each group's wave repeats the step's forward
+// and sweeps its share of the output rows. The most the host rule picks and MJL_OPT_LINEARIZE_GROUPS accepts.
+constexpr int kLinMaxGroups = 16;
 
 extern "C" {
 
@@ -336,6 +343,12 @@ int mjl_batch_set_option(mjlBatch* B, int option, int value) {
   if (option == MJL_OPT_RAY_CHUNK) {
     if (value < 0 || value > 65535) return fail(MJL_ERR_ARG, "ray chunk: 0..65535 rays per wavefront");
     B->ray_chunk = value;
+    return MJL_OK;
+  }
+  if (option == MJL_OPT_LINEARIZE_GROUPS) {
+    if (value < 0 || value > kLinMaxGroups)
+      return fail(MJL_ERR_ARG, "linearize groups: 0..%d row groups per env", kLinMaxGroups);
+    B->lin_groups = value;
     return MJL_OK;
   }
   return fail(MJL_ERR_ARG, "unknown option %d", option);
@@ -1000,19 +1013,29 @@ static int fail_applied(const mjlBatch* B) {
                                    "set MJL_OPT_PER_ENV_MODEL to 0 first");
 }
 
+// The step VJP's per-block scratch (row slab + adjoint scratch): allocated on first use for `blocks` strides and
+// regrown when a later call needs more (mjl_step_jacobian with row groups: nenv x groups), so outside stream
+// capture. A regrow frees the old buffer: graphs captured against it must be captured again.
+static int ensure_adj_scratch(mjlBatch* B, int blocks) {
+  if (B->d_adj_scratch && blocks <= B->adj_blocks) return MJL_OK;
+  const int LD = B->model->nvc == 0 ? DHum::LD : DGen::LD;
+  B->adj_row_floats = row_slab_floats(LD, B->gmax_efc, B->gmax_con);
+  B->adj_row_floats = (B->adj_row_floats + 3) & ~3;
+  B->adj_stride = B->adj_row_floats + adj_scratch_floats(B->gmax_efc, B->gmax_con);
+  if (B->model->nvc == 0) B->adj_stride += DHumV::NV * DHumV::LD;  // lean unrolled replay: M-bar rows
+  B->adj_stride = (B->adj_stride + 3) & ~3;
+  (void)hipFree(B->d_adj_scratch);
+  B->d_adj_scratch = nullptr; B->adj_blocks = 0;
+  hipError_t e = hipMalloc(&B->d_adj_scratch, (size_t)B->adj_stride * blocks * sizeof(float));
+  if (e != hipSuccess) { B->d_adj_scratch = nullptr; return fail(MJL_ERR_HIP, "adjoint scratch: %s", hipGetErrorString(e)); }
+  B->adj_blocks = blocks;
+  return MJL_OK;
+}
+
 template <bool ENV, int TM = 0> static int launch_vjp(mjlBatch* B, const VjpArgs& V0, void* stream,
                                                      const KParams* P0 = nullptr) {
   HIPCHK(hipSetDevice(B->device));
-  if (!B->d_adj_scratch) {
-    const int LD = B->model->nvc == 0 ? DHum::LD : DGen::LD;
-    B->adj_row_floats = row_slab_floats(LD, B->gmax_efc, B->gmax_con);
-    B->adj_row_floats = (B->adj_row_floats + 3) & ~3;
-    B->adj_stride = B->adj_row_floats + adj_scratch_floats(B->gmax_efc, B->gmax_con);
-    if (B->model->nvc == 0) B->adj_stride += DHumV::NV * DHumV::LD;  // lean unrolled replay: M-bar rows
-    B->adj_stride = (B->adj_stride + 3) & ~3;
-    hipError_t e = hipMalloc(&B->d_adj_scratch, (size_t)B->adj_stride * B->nenv * sizeof(float));
-    if (e != hipSuccess) { B->d_adj_scratch = nullptr; return fail(MJL_ERR_HIP, "adjoint scratch: %s", hipGetErrorString(e)); }
-  }
+  if (int rc = ensure_adj_scratch(B, B->nenv)) return rc;
   if (B->vjp_unrolled && !B->d_unr) {
     B->unr_dims.init(B->model->nvc == 0 ? DHum::LD : DGen::LD, B->gmax_efc, B->model->desc.iterations);
     hipError_t e = hipMalloc(&B->d_unr, (size_t)B->unr_dims.stride * B->nenv * sizeof(float));
@@ -1139,6 +1162,39 @@ int mjl_step_vjp_full(mjlBatch* B, const float* g_qpos, const float* g_qvel, con
   if (!B || !g_qpos || !g_qvel || !out_qpos || !out_qvel || !out_ctrl) return fail(MJL_ERR_ARG, "bad argument");
   return launch_vjp<false>(B, vjp_io(nullptr, g_qpos, g_qvel, g_qacc_ws, nullptr, nullptr, out_qpos, out_qvel,
                                      out_qacc_ws, out_ctrl, nullptr, nullptr), stream);
+}
+
+// Row groups per env of mjl_step_jacobian: the forward is repeated by every group, so groups pay only while the
+// envs alone leave SIMDs idle. The rule and the measurements behind it: DESIGN.md "Linearization",
+// profiles/linearize/cost.json.
+static int linearize_groups(const mjlBatch* B) {
+  if (B->lin_groups > 0) return B->lin_groups;
+  int g = B->simds > 0 ? B->simds / B->nenv : 1;
+  return g < 1 ? 1 : (g > kLinMaxGroups ? kLinMaxGroups : g);
+}
+
+// One launch (linearize_kernels.hip): per (env, row group) the step's forward once, then the implicit VJP's reverse
+// passes once per output row.
+int mjl_step_jacobian(mjlBatch* B, const float* mask, const float* ctrl, int flags, float* A, float* Bm, void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (!A && !Bm) return fail(MJL_ERR_ARG, "mjl_step_jacobian: A and B are both NULL");
+  if (flags & ~MJL_JAC_TANGENT) return fail(MJL_ERR_ARG, "mjl_step_jacobian: flags = %d: 0 or MJL_JAC_TANGENT", flags);
+  if (applied_attached(B)) return fail_applied(B);
+  HIPCHK(hipSetDevice(B->device));
+  const int G = linearize_groups(B);
+  if ((long long)B->nenv * G > 0x7fffffffLL) return fail(MJL_ERR_ARG, "mjl_step_jacobian: %d envs x %d row groups", B->nenv, G);
+  if (int rc = ensure_adj_scratch(B, B->nenv * G)) return rc;
+  KParams P = make_params(B);
+  LinArgs L;
+  L.ctrl = ctrl ? ctrl : B->s.ctrl; L.mask = mask; L.A = A; L.B = Bm;
+  L.scratch = B->d_adj_scratch; L.scratch_stride = B->adj_stride; L.row_floats = B->adj_row_floats;
+  L.groups = G; L.tangent = (flags & MJL_JAC_TANGENT) != 0;
+  if (B->model->nvc == 0)
+    hipLaunchKernelGGL(linearize_kernel<DHumV>, dim3(B->nenv * G), dim3(64), 0, (hipStream_t)stream, P, L);
+  else
+    hipLaunchKernelGGL(linearize_kernel<DGen>, dim3(B->nenv * G), dim3(64), 0, (hipStream_t)stream, P, L);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
 }
 
 int mjl_env_step_vjp_full(mjlBatch* B, const float* act, const float* g_qpos, const float* g_qvel,

@@ -65,7 +65,9 @@ SENSOR_STAGE = {k[15:].lower(): v for k, v in _E.items() if k.startswith("MJL_SE
 SENSOR_OBJ = {k[8:].lower(): v for k, v in _E.items() if k.startswith("MJL_OBJ_")}
 RAY_STATIC = _E["MJL_RAY_STATIC"]  # mjl_ray / mjl_ray_scan flags
 SCAN_ALIGN = {k[9:].lower(): v for k, v in _E.items() if k.startswith("MJL_SCAN_")}  # "pose", "yaw"
-JAC_FRAME = {k[8:].lower(): v for k, v in _E.items() if k.startswith("MJL_JAC_")}  # mjl_jac: "world", "local"
+JAC_TANGENT = _E["MJL_JAC_TANGENT"]  # mjl_step_jacobian flags
+# mjl_jac: "world", "local"
+JAC_FRAME = {k[8:].lower(): v for k, v in _E.items() if k.startswith("MJL_JAC_") and k != "MJL_JAC_TANGENT"}
 INV_DISCRETE = _E["MJL_INV_DISCRETE"]  # mjl_inverse flags
 
 

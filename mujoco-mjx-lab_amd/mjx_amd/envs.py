@@ -219,6 +219,20 @@ class HumanoidEnv:
                              torch.zeros((self.num_envs, self.sys.nv), device=self.obs.device))
         return inverse(self.sys, self.data, qacc, discrete, mask, self._inverse, with_constraint=True)
 
+    def transition(self, mask: Optional[torch.Tensor] = None):
+        """Linearization of the physics step at the envs' current state and stored ctrl (mjx.transition): (A
+        [num_envs, 2nv, 2nv], B [num_envs, 2nv, nu]) in tensors this env owns (zeros at first, written again by
+        every call). It is mjx.step's derivative: the env's action flip / clip and its reward are not part of it,
+        and it covers one physics step, so an env with n_frames != 1 raises. One launch that writes nothing of the
+        envs' state; after one eager call (which allocates the scratch) it can be captured with the step."""
+        from .mjx import transition
+        if self.n_frames != 1:
+            raise MjlError(f"transition() linearises one physics step; this env runs n_frames = {self.n_frames}")
+        if getattr(self, "_transition", None) is None:
+            n, nv, nu, dev = self.num_envs, self.sys.nv, self.sys.nu, self.obs.device
+            self._transition = (torch.zeros((n, 2 * nv, 2 * nv), device=dev), torch.zeros((n, 2 * nv, nu), device=dev))
+        return transition(self.sys, self.data, None, mask, self._transition)
+
     def scan(self, frame, pattern, align: str = "pose", flg_static: bool = True, bodyexclude="self",
              cutoff: float = 0.0, mask: Optional[torch.Tensor] = None):
         """Range scan of the envs' current state (mjx.ray_scan): `pattern` = (lpnt, lvec) [nray, 3] in the frame

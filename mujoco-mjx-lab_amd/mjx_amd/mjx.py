@@ -805,6 +805,57 @@ def step_vjp(sys: Model, d: Data, g_qpos: torch.Tensor, g_qvel: torch.Tensor):
     return oq, ov, oc
 
 
+def _step_jacobian(sys: Model, d: Data, ctrl, mask, out, flags: int, nx: int):
+    """mjl_step_jacobian into (A [nenv, nx, nx], B [nenv, nx, nu]); `out` = (A, B), either None to skip it."""
+    if ctrl is not None:
+        ctrl = torch.as_tensor(ctrl, dtype=torch.float32).to(d.device).contiguous()
+        if tuple(ctrl.shape) != (d.nenv, sys.nu):
+            raise MjlError(f"ctrl must have shape {(d.nenv, sys.nu)}")
+    shapes = ((d.nenv, nx, nx), (d.nenv, nx, sys.nu))
+    if out is None:
+        outs = [(torch.empty if mask is None else torch.zeros)(s, dtype=torch.float32, device=d.device) for s in shapes]
+    else:
+        outs = list(out) if isinstance(out, (tuple, list)) else None
+        if outs is None or len(outs) != 2 or (outs[0] is None and outs[1] is None):
+            raise MjlError("out is (A, B), at most one of them None")
+        for o, s, what in zip(outs, shapes, "AB"):
+            if o is not None and (tuple(o.shape) != s or o.device != d.device or o.dtype != torch.float32):
+                raise MjlError(f"out {what} must be float32 of shape {s} on {d.device}")
+    mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
+    check(lib().mjl_step_jacobian(d.handle, _ptr(mk), _ptr(ctrl), flags, _ptr(outs[0]), _ptr(outs[1]), _stream()))
+    return outs[0], outs[1]
+
+
+def transition(sys: Model, d: Data, ctrl=None, mask: Optional[torch.Tensor] = None, out=None):
+    """mjd_transitionFD's matrices of one mjx.step at the batch's current state, exact rather than by finite
+    differences: (A [nenv, 2nv, 2nv], B [nenv, 2nv, nu]) with the state x = (dq, qvel) in the tangent space (a free
+    joint's rotation as a body-frame rotation vector, mj_integratePos / mj_differentiatePos). ctrl [nenv, nu]:
+    where to linearise (None: the stored ctrl). out = (A, B) to write into; one of them may be None, and is then
+    neither computed nor returned (None comes back in its place). The constraint solve is differentiated at its
+    converged active set, as step_vjp does by default. Rows of envs with mask <= 0.5 keep what `out` held (fresh
+    tensors are zeros under a mask). Nothing of `d` is written. One launch; the first call allocates scratch, so it
+    happens outside graph capture. See include/mjx355.h mjl_step_jacobian (MJL_JAC_TANGENT)."""
+    return _step_jacobian(sys, d, ctrl, mask, out, abi.JAC_TANGENT, 2 * sys.nv)
+
+
+def step_jacobian(sys: Model, d: Data, ctrl=None, mask: Optional[torch.Tensor] = None, out=None) -> torch.Tensor:
+    """jax.jacobian(mjx.step) in raw coordinates: J [nenv, nq+nv, nq+nv+nu], rows (qpos', qvel'), columns (qpos,
+    qvel, ctrl), the oracle's Oracle.step_jacobian per env. out: a tensor of that shape to write into. ctrl and
+    mask as transition(). Assembled from mjl_step_jacobian's two raw outputs (one launch and one copy each)."""
+    nx, shape = sys.nq + sys.nv, (d.nenv, sys.nq + sys.nv, sys.nq + sys.nv + sys.nu)
+    if out is not None and (tuple(out.shape) != shape or out.device != d.device or out.dtype != torch.float32):
+        raise MjlError(f"out must be float32 of shape {shape} on {d.device}")
+    A, B = _step_jacobian(sys, d, ctrl, mask, None, 0, nx)
+    if out is None:
+        return torch.cat([A, B], dim=2)
+    if mask is None:
+        out[:, :, :nx], out[:, :, nx:] = A, B
+    else:
+        keep = (mask.to(device=d.device, dtype=torch.float32) > 0.5).view(-1, 1, 1)
+        out.copy_(torch.where(keep, torch.cat([A, B], dim=2), out))
+    return out
+
+
 def step_vjp_full(sys: Model, d: Data, g_qpos: torch.Tensor, g_qvel: torch.Tensor, g_qacc_ws: torch.Tensor):
     """step_vjp with the carried warm start (mjl_step_vjp_full): cotangents of (qpos', qvel',
     qacc_warmstart') -> (qpos, qvel, qacc_warmstart, ctrl)."""
