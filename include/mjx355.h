@@ -718,6 +718,60 @@ enum { MJL_JAC_TANGENT = 1 };
 int mjl_step_jacobian(mjlBatch* batch, const float* mask, const float* ctrl, int flags, float* A, float* B,
                       void* stream);
 
+/* Batched inverse kinematics: a damped least-squares (Gauss-Newton) solve per env for a qpos that brings ntask body
+ * or site frames to target positions and / or orientations. The whole solve, every iteration of it, is one launch
+ * of one wavefront per env. Buffers (float32 / int32, device, read at execution time, row-major):
+ *   body        [ntask], ntask in 1..32, shared by all envs: the carrying body of each task. A site is its body with
+ *               offset = site_pos, as mjl_jac with MJL_JAC_LOCAL; an orientation target is the body frame's.
+ *   offset      [ntask, 3] or NULL (the body origins): the task point in the body's frame
+ *   target_pos  [nenv, ntask, 3] or NULL; target_quat [nenv, ntask, 4] or NULL (normalised on read, a zero
+ *               quaternion reads as the identity): world-frame targets, not both NULL
+ *   weight      [ntask, 2] or NULL: (w_pos, w_rot) per task, each >= 0; NULL = 1 where the matching target array is
+ *               given. A weight that is not > 0, or a NULL target array, drops those three rows.
+ *   qpos_start  [nenv, nq] or NULL (the batch's current qpos): the start of the solve
+ *   qpos_ref    [nenv, nq] or NULL (the model's qpos0): the posture that `posture` pulls toward
+ *   dofmask     bit d set: dof d may move; -1 (all bits) = every dof
+ *   qpos_out    [nenv, nq], required: the solution; err [nenv, ntask, 6] or NULL: the unweighted residual (e_p ; e_r)
+ *               at the returned qpos_out, zeros in rows without a target array; niter [nenv] or NULL: the iterations
+ *               taken.
+ * One iteration, all in float32 (fmaf where "fma" is written) in this order:
+ *   1. Kinematics of the iterate q, as mjl_jac's: the free quaternion normalised for the pass (q itself keeps its
+ *      entries), every hinge about its world axis.
+ *   2. Residuals, per task t with body b: x = xpos_b + R_b offset_t, e_p = target_pos - x; q_e = target_quat (x)
+ *      conj(xquat_b), negated when its scalar part is negative, e_r = its world-frame rotation vector
+ *      v * (2 atan2(|v|, w) / |v|), v the vector part (zero when |v| < 1e-15): mju_quat2Vel at dt = 1.
+ *      res = max_t max(w_pos |e_p|, w_rot |e_r|) over the rows that are not dropped.
+ *   3. Stop: iteration k (0-based) ends the solve before its update when k = iterations, or when tol > 0 and res <
+ *      tol; niter = k. The test is the same for the whole wavefront.
+ *   4. Normal equations H dq = g. With Jp, Jr exactly mjl_jac's jacp, jacr of the point, the weighted rows are
+ *      c_r = w J[r, :] and the weighted residuals w e[r], r = 0..5 (three position rows, then three rotation rows).
+ *      H starts as (damping + posture) I and g as posture * delta. Then task by task in index order and row by row,
+ *      H[i][j] = fma(c_r[i], c_r[j], H[i][j]) and g[i] = fma(c_r[i], w e[r], g[i]): both triangles of H take the
+ *      same chain over the same operands, so H is symmetric bit for bit. delta = mj_differentiatePos(qpos_ref, q),
+ *      the tangent from q toward the reference under the maps MJL_JAC_TANGENT documents: hinge coordinates and the
+ *      free position subtract (ref - q), the free quaternion gives the body-frame rotation vector of conj(q) (x)
+ *      ref (both normalised, sign as in step 2); with posture = 0 delta is not evaluated. A dof outside dofmask, or
+ *      at or past nv, has the identity's row and column and g = 0.
+ *   5. Step: dq = H^-1 g by mjl_mass_matrix's Cholesky factor and substitutions on the 32 x 32 matrix. When
+ *      max_step > 0 and s = max_d |dq_d| > max_step, dq is multiplied by max_step / s.
+ *   6. Update q <- mj_integratePos(q, dq, 1) over the dofs of dofmask: hinge coordinates and the free position add;
+ *      the free quaternion becomes q (x) exp(dq_rot) in the body frame, renormalised, as the step integrates it
+ *      (its entries left alone when dq_rot is zero, as it is when none of its three dofs is in dofmask or moves a
+ *      task). With MJL_IK_LIMITS a limited hinge is then clamped to jnt_range.
+ * iterations = 0 copies the start to qpos_out bit for bit and evaluates err. tol = 0 always runs `iterations`
+ * iterations. Dofs outside dofmask keep their qpos entries bit for bit.
+ * Nothing of the batch is written. Per-env model parameters and applied forces do not matter (no geometric field is
+ * per-env). A body id outside 0..nbody-1 in any task gives NaN rows in qpos_out and err for every env and niter = 0
+ * (mjl_jac's rule). Envs with mask <= 0.5 keep their rows of every output (mask NULL = all envs). No allocation, no
+ * synchronisation, capturable.
+ * MJL_ERR_ARG: a null batch, body or qpos_out; ntask outside 1..32; both target arrays NULL; iterations outside
+ * 0..1024; damping <= 0, posture < 0, max_step < 0 or tol < 0 (or not finite); unknown flag bits. */
+enum { MJL_IK_LIMITS = 1 };
+int mjl_ik(mjlBatch* batch, const float* mask, int ntask, const int32_t* body, const float* offset,
+           const float* target_pos, const float* target_quat, const float* weight, const float* qpos_start,
+           const float* qpos_ref, int32_t dofmask, int iterations, float damping, float posture, float max_step,
+           float tol, int flags, float* qpos_out, float* err, int32_t* niter, void* stream);
+
 /* The persistent per-env state (what a step reads and writes: Data.qpos, qvel, qacc_warmstart,
  * time, plus the env aux) as packed rows [nenv, mjl_state_size] = [qpos | qvel | qacc_warmstart |
  * aux | time]: the APG remat tape entry (train_apg.py:187-189 checkpoints each step's carry).

@@ -24,6 +24,7 @@
 #include "sensor_kernels.hip"
 #include "body_kernels.hip"
 #include "dyn_kernels.hip"
+#include "ik_kernels.hip"
 #include "taskspace_kernels.hip"
 #include "inverse_kernels.hip"
 #include "linearize_kernels.hip"
@@ -723,6 +724,34 @@ int mjl_centroidal(mjlBatch* B, const float* mask, int nsub, const int32_t* body
   A.mask = mask; A.nenv = B->nenv; A.nsub = nsub; A.body = body;
   A.jac_com = jac_com; A.angmom_mat = angmom_mat; A.bias = bias;
   hipLaunchKernelGGL(centroidal_kernel, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
+}
+
+// One launch (ik_kernels.hip): every iteration of every env's solve on chip, nothing of the batch written.
+int mjl_ik(mjlBatch* B, const float* mask, int ntask, const int32_t* body, const float* offset, const float* target_pos,
+           const float* target_quat, const float* weight, const float* qpos_start, const float* qpos_ref,
+           int32_t dofmask, int iterations, float damping, float posture, float max_step, float tol, int flags,
+           float* qpos_out, float* err, int32_t* niter, void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (!body) return fail(MJL_ERR_ARG, "mjl_ik: body is required");
+  if (!qpos_out) return fail(MJL_ERR_ARG, "mjl_ik: qpos_out is required");
+  if (ntask < 1 || ntask > kIkMaxTask) return fail(MJL_ERR_ARG, "mjl_ik: ntask = %d outside 1..%d", ntask, kIkMaxTask);
+  if (!target_pos && !target_quat) return fail(MJL_ERR_ARG, "mjl_ik: target_pos and target_quat are both NULL");
+  if (iterations < 0 || iterations > 1024) return fail(MJL_ERR_ARG, "mjl_ik: iterations = %d outside 0..1024", iterations);
+  if (!(damping > 0.f) || !std::isfinite(damping)) return fail(MJL_ERR_ARG, "mjl_ik: damping = %g: a finite value > 0", damping);
+  if (!(posture >= 0.f) || !std::isfinite(posture)) return fail(MJL_ERR_ARG, "mjl_ik: posture = %g: a finite value >= 0", posture);
+  if (!(max_step >= 0.f) || !std::isfinite(max_step)) return fail(MJL_ERR_ARG, "mjl_ik: max_step = %g: a finite value >= 0", max_step);
+  if (!(tol >= 0.f) || !std::isfinite(tol)) return fail(MJL_ERR_ARG, "mjl_ik: tol = %g: a finite value >= 0", tol);
+  if (flags & ~MJL_IK_LIMITS) return fail(MJL_ERR_ARG, "mjl_ik: flags = %d: 0 or MJL_IK_LIMITS", flags);
+  HIPCHK(hipSetDevice(B->device));
+  IkArgs A;
+  A.m = B->d_model; A.tab = B->d_dyntab; A.qstart = qpos_start ? qpos_start : B->s.qpos; A.qref = qpos_ref;
+  A.mask = mask; A.nenv = B->nenv; A.ntask = ntask; A.body = body; A.offset = offset; A.tpos = target_pos;
+  A.tquat = target_quat; A.weight = weight; A.dofmask = (uint32_t)dofmask; A.iterations = iterations;
+  A.limits = (flags & MJL_IK_LIMITS) != 0; A.damping = damping; A.posture = posture; A.max_step = max_step; A.tol = tol;
+  A.qout = qpos_out; A.err = err; A.niter = niter;
+  hipLaunchKernelGGL(ik_kernel, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
   HIPCHK(hipGetLastError());
   return MJL_OK;
 }

@@ -69,6 +69,7 @@ JAC_TANGENT = _E["MJL_JAC_TANGENT"]  # mjl_step_jacobian flags
 # mjl_jac: "world", "local"
 JAC_FRAME = {k[8:].lower(): v for k, v in _E.items() if k.startswith("MJL_JAC_") and k != "MJL_JAC_TANGENT"}
 INV_DISCRETE = _E["MJL_INV_DISCRETE"]  # mjl_inverse flags
+IK_LIMITS = _E["MJL_IK_LIMITS"]  # mjl_ik flags
 
 
 class UnsupportedModel(ValueError):

@@ -166,6 +166,29 @@ class HumanoidEnv:
         tabs, out = bufs[key]
         return jac_local(self.sys, self.data, frames, offset, mask, out, _dev=tabs)
 
+    def ik(self, frames, target_pos=None, target_quat=None, offset=None, weight=None, qpos_start=None, qpos_ref=None,
+           dofs=None, iterations: int = 20, damping: float = 1e-3, posture: float = 0.0, max_step: float = 0.0,
+           tol: float = 0.0, limits: bool = True, mask: Optional[torch.Tensor] = None):
+        """Inverse kinematics from the envs' current qpos (mjx.ik; qpos_start overrides the start): IKResult(qpos,
+        err, niter) in tensors this env owns. The tasks' device tables and the three outputs are allocated (zeros)
+        at the first call with these (frames, offset, weight) and written again by every later one; targets given
+        as device tensors are read at execution time. After one eager call it is one launch that writes nothing of
+        the envs' state and can be captured with the step, as jac()."""
+        from .mjx import ik, ik_tables
+        bodies, local, conj, w = ik_tables(self.sys, frames, offset, weight)
+        key = (tuple(bodies), local.tobytes(), None if conj is None else conj.tobytes(), None if w is None else w.tobytes())
+        bufs = self.__dict__.setdefault("_ik_bufs", {})
+        if key not in bufs:
+            dev, n, p = self.obs.device, self.num_envs, len(bodies)
+            bufs[key] = ((torch.tensor(bodies, dtype=torch.int32, device=dev), torch.tensor(local, device=dev),
+                          None if conj is None else torch.tensor(conj, device=dev),
+                          None if w is None else torch.tensor(w, device=dev)),
+                         (torch.zeros((n, self.sys.nq), device=dev), torch.zeros((n, p, 6), device=dev),
+                          torch.zeros((n,), dtype=torch.int32, device=dev)))
+        tabs, out = bufs[key]
+        return ik(self.sys, self.data, frames, target_pos, target_quat, offset, weight, qpos_start, qpos_ref, dofs,
+                  iterations, damping, posture, max_step, tol, limits, mask, out, _dev=tabs)
+
     def jac_dot(self, frames, offset=None, mask: Optional[torch.Tensor] = None):
         """Time derivatives of jac()'s Jacobians and the velocity-product term (mjx.jac_dot_local): (jacp_dot,
         jacr_dot, jdotv) in tensors this env owns, allocated (zeros) at the first call with these (frames,

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -854,6 +854,135 @@ def step_jacobian(sys: Model, d: Data, ctrl=None, mask: Optional[torch.Tensor] =
         keep = (mask.to(device=d.device, dtype=torch.float32) > 0.5).view(-1, 1, 1)
         out.copy_(torch.where(keep, torch.cat([A, B], dim=2), out))
     return out
+
+
+MAX_IK_TASKS = 32  # mjl_ik's ntask
+
+
+class IKResult(NamedTuple):
+    """What `ik` returns: the solution, the residual there and the iterations taken."""
+    qpos: torch.Tensor             # [nenv, nq]
+    err: Optional[torch.Tensor]    # [nenv, ntask, 6]: (e_p ; e_r), world frame, unweighted
+    niter: Optional[torch.Tensor]  # [nenv] int32
+
+
+def ik_dofmask(sys: Model, dofs) -> int:
+    """mjl_ik's dofmask of `dofs`: None (every dof), a bool list over nv, a list of dof indices, or joint names (a
+    free joint stands for its six dofs)."""
+    nv = sys.nv
+    if dofs is None:
+        return (1 << 32) - 1
+    dofs = dofs.tolist() if hasattr(dofs, "tolist") else list(dofs)
+    if len(dofs) == nv and all(isinstance(x, bool) for x in dofs):
+        return sum(1 << i for i, x in enumerate(dofs) if x)
+    mask = 0
+    for x in dofs:
+        if isinstance(x, str):
+            j = sys.m.name2id("joint", x)
+            if j < 0:
+                raise ValueError(f"no joint named {x!r}")
+            a = int(sys.m.arrays["jnt_dofadr"][j])
+            ids = range(a, a + (6 if sys.m.arrays["jnt_type"][j] == mjcf.JNT_FREE else 1))
+        else:
+            if isinstance(x, bool):
+                raise ValueError(f"a bool list over the dofs has {nv} entries, not {len(dofs)}")
+            ids = [int(x)]
+        for i in ids:
+            if not 0 <= i < nv:
+                raise ValueError(f"dof {i} outside 0..{nv - 1}")
+            mask |= 1 << i
+    return mask
+
+
+def ik_tables(sys: Model, frame, offset=None, weight=None):
+    """Host tables of ik's tasks: (body ids, body-frame offsets [ntask, 3] float32, conj(site_quat) [ntask, 4] float32
+    or None when every frame is a body, weights [ntask, 2] float32 or None). frame / offset as jac_local's."""
+    import numpy as np
+    bodies, local = jac_frames(sys, frame, offset)
+    if len(bodies) > MAX_IK_TASKS:
+        raise ValueError(f"ik takes 1..{MAX_IK_TASKS} tasks, not {len(bodies)}")
+    single = isinstance(frame, str) or (isinstance(frame, tuple) and len(frame) == 2 and isinstance(frame[0], str)
+                                        and frame[0] in ("xbody", "site") and not isinstance(frame[1], str))
+    conj, any_site = np.tile(np.float32([1, 0, 0, 0]), (len(bodies), 1)), False
+    for k, f in enumerate([frame] if single else list(frame)):
+        objtype, i, _ = scan_frame(sys, f)
+        if objtype == abi.SENSOR_OBJ["site"]:
+            q = np.asarray(sys.m.arrays["site_quat"][i], np.float64)
+            conj[k] = np.float32([q[0], -q[1], -q[2], -q[3]] / np.linalg.norm(q))
+            any_site = True
+    w = None
+    if weight is not None:
+        w = np.float32(np.broadcast_to(np.asarray(weight.cpu() if torch.is_tensor(weight) else weight, np.float64),
+                                       (len(bodies), 2)))
+        if not (w >= 0).all():
+            raise ValueError("ik weights must be >= 0")
+    return bodies, local, conj if any_site else None, w
+
+
+def _qmul_t(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    aw, ax, ay, az = a.unbind(-1)
+    bw, bx, by, bz = b.unbind(-1)
+    return torch.stack((aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                        aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw), -1)
+
+
+def ik(sys: Model, d: Data, frame, target_pos=None, target_quat=None, offset=None, weight=None, qpos_start=None,
+       qpos_ref=None, dofs=None, iterations: int = 20, damping: float = 1e-3, posture: float = 0.0,
+       max_step: float = 0.0, tol: float = 0.0, limits: bool = True, mask: Optional[torch.Tensor] = None, out=None,
+       _dev=None) -> IKResult:
+    """Batched inverse kinematics: per env a qpos that brings the frames (bodies or sites: names or ("xbody" | "site",
+    id) pairs, as jac_local's, with `offset` in the frame) to the world targets target_pos [nenv, ntask, 3] and / or
+    target_quat [nenv, ntask, 4] (the frame's own orientation; [nenv, 3] / [nenv, 4] with one frame). A damped
+    Gauss-Newton iteration, dq = (J'W'WJ + (damping + posture) I)^-1 (J'W'W e + posture (qpos_ref - q)), run
+    `iterations` times, or until every weighted residual is below tol > 0, inside one launch. weight [ntask, 2]:
+    (w_pos, w_rot) per task; qpos_start: None = the batch's current qpos; qpos_ref: None = qpos0; dofs: the dofs that
+    may move (see ik_dofmask); max_step > 0 bounds max |dq| of an iteration; limits: clamp limited hinges to
+    jnt_range. Nothing of `d` is written. Returns IKResult(qpos, err, niter); out: (qpos, err, niter) to write into,
+    err and niter may be None. Rows of envs with mask <= 0.5 keep what `out` held (fresh tensors are zeros under a
+    mask). Capturable when the targets and out are device tensors. See include/mjx355.h mjl_ik."""
+    if _dev is None:
+        bodies, local, conj, w = ik_tables(sys, frame, offset, weight)
+        dev = d.device
+        _dev = (torch.tensor(bodies, dtype=torch.int32, device=dev), torch.tensor(local, device=dev),
+                None if conj is None else torch.tensor(conj, device=dev), None if w is None else torch.tensor(w, device=dev))
+    bt, lt, cq, wt = _dev
+    n = bt.shape[0]
+
+    def arg(t, shape, what):
+        if t is None:
+            return None
+        t = torch.as_tensor(t, dtype=torch.float32).to(d.device)
+        if t.dim() == len(shape) - 1 and n == 1 and len(shape) == 3:
+            t = t.unsqueeze(1)
+        if tuple(t.shape) != shape:
+            raise MjlError(f"{what} must have shape {shape}")
+        return t.contiguous()
+    tp = arg(target_pos, (d.nenv, n, 3), "target_pos")
+    tq = arg(target_quat, (d.nenv, n, 4), "target_quat")
+    if tp is None and tq is None:
+        raise MjlError("ik needs target_pos or target_quat")
+    if tq is not None and cq is not None:
+        tq = _qmul_t(tq, cq.unsqueeze(0)).contiguous()  # the site's target -> its body's
+    qs = arg(qpos_start, (d.nenv, sys.nq), "qpos_start")
+    qr = arg(qpos_ref, (d.nenv, sys.nq), "qpos_ref")
+    shapes = ((d.nenv, sys.nq), (d.nenv, n, 6), (d.nenv,))
+    if out is None:
+        new = torch.zeros if mask is not None else torch.empty
+        out = (new(shapes[0], dtype=torch.float32, device=d.device), new(shapes[1], dtype=torch.float32, device=d.device),
+               new(shapes[2], dtype=torch.int32, device=d.device))
+    qo, eo, no = (tuple(out) + (None, None))[:3]
+    for t, s, what in zip((qo, eo, no), shapes, ("qpos", "err", "niter")):
+        if t is None and what == "qpos":
+            raise MjlError("ik needs the qpos output")
+        if t is not None and (tuple(t.shape) != s or t.device != d.device):
+            raise MjlError(f"{what} must have shape {s} on {d.device}")
+    mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
+    dm = ik_dofmask(sys, dofs)
+    check(lib().mjl_ik(d.handle, _ptr(mk), n, _iptr(bt), _ptr(lt), _ptr(tp), _ptr(tq), _ptr(wt), _ptr(qs), _ptr(qr),
+                       dm - (1 << 32) if dm >= 1 << 31 else dm, int(iterations), float(damping), float(posture),
+                       float(max_step), float(tol), abi.IK_LIMITS if limits else 0, _ptr(qo),
+                       _ptr(eo), None if no is None else _iptr(no), _stream()))
+    return IKResult(qo, eo, no)
 
 
 def step_vjp_full(sys: Model, d: Data, g_qpos: torch.Tensor, g_qvel: torch.Tensor, g_qacc_ws: torch.Tensor):
