@@ -224,9 +224,13 @@ int mjl_batch_nenv(const mjlBatch* batch);
  * mjl_ray_scan, 0..65535; 0 = the library's choice. The results do not depend on it.
  * MJL_OPT_LINEARIZE_GROUPS (default 0, test and tuning hook of tools/linearize_bench.py): value = row groups per
  * env of mjl_step_jacobian, 0..16; 0 = the library's choice from the env count. The results do not depend on it,
- * bit for bit. */
+ * bit for bit.
+ * MJL_OPT_DISTANCE_CHUNK (default 0, test and tuning hook of tools/distance_bench.py): value = geom pairs per
+ * wavefront of mjl_geom_distance, 0..65535; 0 = the library's choice. The results do not depend on it, bit for
+ * bit. */
 enum { MJL_OPT_STORE_DERIVED = 0, MJL_OPT_FORCE_GLOBAL_ROWS = 1, MJL_OPT_VJP_UNROLLED = 2, MJL_OPT_RESET_POOL = 3,
-       MJL_OPT_VJP_TAPE = 4, MJL_OPT_PER_ENV_MODEL = 5, MJL_OPT_RAY_CHUNK = 6, MJL_OPT_LINEARIZE_GROUPS = 7 };
+       MJL_OPT_VJP_TAPE = 4, MJL_OPT_PER_ENV_MODEL = 5, MJL_OPT_RAY_CHUNK = 6, MJL_OPT_LINEARIZE_GROUPS = 7,
+       MJL_OPT_DISTANCE_CHUNK = 8 };
 int mjl_batch_set_option(mjlBatch* batch, int option, int value);
 
 /* Per-env model parameters (domain randomisation; in MJX jax.vmap(step, in_axes=(model_axes, 0)) over a
@@ -522,6 +526,41 @@ int mjl_ray(mjlBatch* batch, const float* mask, int nray, const float* pnt, cons
 int mjl_ray_scan(mjlBatch* batch, const float* mask, int objtype, int objid, int align, int nray, const float* lpnt,
                  const float* lvec, int flags, int bodyexclude, float cutoff, float* dist, int32_t* geomid,
                  float* hitpos, void* stream);
+
+/* Signed distances between geoms of the batch's current state: mj_geomDistance (the distance / normal / fromto
+ * sensors' computation) for npair geom pairs per env, with the gradient. Buffers (float32 / int32, device, read at
+ * execution time): geom1, geom2 [npair], shared by all envs; dist [nenv, npair], required; fromto [nenv, npair, 6],
+ * normal [nenv, npair, 3], jac [nenv, npair, nv], each may be NULL (a NULL output costs no stores).
+ * Geometry: the geoms are posed by forward kinematics of the batch's current qpos, run in the same launch
+ * (mjl_jac's tree pass). No mjl_forward is needed first, the stored xpos / xquat are neither read nor written, so
+ * the call is correct right after mjl_env_step. While MJL_OPT_PER_ENV_MODEL is on nothing changes: no geometric
+ * field is among the six per-env fields; applied forces do not matter either.
+ *   dist    the signed distance between the two surfaces, negative when the geoms overlap
+ *   fromto  [0:3] `from`, on geom1's surface; [3:6] `to`, on geom2's, whatever the order of the two types
+ *   normal  the unit vector from geom1 towards geom2: to = from + dist * normal, also when dist < 0
+ *   jac     normal' (jacp(to, body of geom2) - jacp(from, body of geom1)), jacp as mjl_jac defines it: jac qvel is
+ *           the rate of dist
+ * Closed forms per pair of types (float32):
+ *   plane - sphere / capsule  the plane is its half-space. The capsule's axis end nearer to the plane decides (a
+ *                             sphere's centre; equal ends: the +z end): dist = (end - plane point) . plane normal - r,
+ *                             the geom's witness is end - r plane normal, the plane's is that point's foot on the
+ *                             plane, normal = +- the plane's normal (+ when the plane is geom1)
+ *   sphere / capsule pairs    pa, pb the closest points of the two axis segments (a sphere's is its centre): dist =
+ *                             |pb - pa| - (r1 + r2), normal = (pb - pa) / |pb - pa|, from = pa + r1 normal, to = pb -
+ *                             r2 normal. Parallel axes have a segment of closest points; one pair of them is returned
+ *   coincident axis points    (|pb - pa|^2 <= 1e-30: no direction is defined) dist = -(r1 + r2) exactly, normal =
+ *                             world +z (0, 0, 1), from / to as above
+ * distmax: when the distance exceeds it, dist = distmax and fromto, normal and jac of the pair are zeros, as MuJoCo
+ * returns; +inf switches the cap off.
+ * A pair whose ids are out of 0..ngeom-1, equal, or both planes gets dist = NaN and zeros in fromto, normal and
+ * jac; the ids are checked in the kernel before anything is read through them (they are device memory, the host
+ * cannot check them).
+ * Envs with mask <= 0.5 keep their output rows (mask NULL = all envs). One launch, no allocation, no
+ * synchronisation, capturable.
+ * MJL_ERR_ARG: a null batch, dist, geom1 or geom2; npair outside 1..65535; distmax not greater than 0, or NaN.
+ * MJL_ERR_UNSUPPORTED: a model with a geom that is no plane, sphere or capsule (the rays' rule). */
+int mjl_geom_distance(mjlBatch* batch, const float* mask, int npair, const int32_t* geom1, const int32_t* geom2,
+                      float distmax, float* dist, float* fromto, float* normal, float* jac, void* stream);
 
 /* Replaces mjx.step (src/envs.py:345): ctrl (device [nenv, nu], may be NULL = keep current)
  * -> forward + integrate, state updated in place. */

@@ -29,6 +29,7 @@
 #include "inverse_kernels.hip"
 #include "linearize_kernels.hip"
 #include "ray_kernels.hip"
+#include "distance_kernels.hip"
 #include "model_host.h"
 
 using namespace mjl;
@@ -126,6 +127,7 @@ struct mjlBatch {
   BodyTab* d_bodytab;         // body_iquat beside the model block (mjl_body_data)
   DynTab* d_dyntab;           // body_dofmask beside the model block (mjl_jac)
   int ray_chunk;              // MJL_OPT_RAY_CHUNK: rays per wavefront of mjl_ray / mjl_ray_scan, 0 = kRayChunk
+  int dist_chunk;             // MJL_OPT_DISTANCE_CHUNK: pairs per wavefront of mjl_geom_distance, 0 = kDistChunk
 };
 
 // one launch of the per-env block builder: `fill` copies the shared block into every env's
@@ -344,6 +346,11 @@ int mjl_batch_set_option(mjlBatch* B, int option, int value) {
   if (option == MJL_OPT_RAY_CHUNK) {
     if (value < 0 || value > 65535) return fail(MJL_ERR_ARG, "ray chunk: 0..65535 rays per wavefront");
     B->ray_chunk = value;
+    return MJL_OK;
+  }
+  if (option == MJL_OPT_DISTANCE_CHUNK) {
+    if (value < 0 || value > 65535) return fail(MJL_ERR_ARG, "distance chunk: 0..65535 pairs per wavefront");
+    B->dist_chunk = value;
     return MJL_OK;
   }
   if (option == MJL_OPT_LINEARIZE_GROUPS) {
@@ -835,6 +842,40 @@ int mjl_ray_scan(mjlBatch* B, const float* mask, int objtype, int objid, int ali
   A.flags = flags; A.bodyexclude = bodyexclude; A.cutoff = cutoff;
   A.dist = dist; A.geomid = geomid; A.hitpos = hitpos;
   return launch_rays(B, A, stream);
+}
+
+// Pairs per wavefront of geom_distance_kernel (distance_kernels.hip) unless MJL_OPT_DISTANCE_CHUNK says otherwise:
+// every chunk's wavefront repeats the env's kinematics. DESIGN.md "Geom distance" has the measurement behind the value.
+constexpr int kDistChunk = 64;
+
+// One launch (distance_kernels.hip): forward kinematics of the current qpos inside the kernel, nothing of the
+// batch written.
+int mjl_geom_distance(mjlBatch* B, const float* mask, int npair, const int32_t* geom1, const int32_t* geom2,
+                      float distmax, float* dist, float* fromto, float* normal, float* jac, void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (!dist) return fail(MJL_ERR_ARG, "mjl_geom_distance: dist is required");
+  if (!geom1 || !geom2) return fail(MJL_ERR_ARG, "mjl_geom_distance: geom1 and geom2 are required");
+  if (npair < 1 || npair > 65535) return fail(MJL_ERR_ARG, "mjl_geom_distance: npair = %d outside 1..65535", npair);
+  if (!(distmax > 0.f)) return fail(MJL_ERR_ARG, "mjl_geom_distance: distmax = %g: a value > 0 (+inf: no cap)", distmax);
+  const mjlModelDesc& d = B->model->desc;
+  for (int g = 0; g < d.ngeom; g++)
+    if (d.geom_type[g] != MJL_GEOM_PLANE && d.geom_type[g] != MJL_GEOM_SPHERE && d.geom_type[g] != MJL_GEOM_CAPSULE)
+      return fail(MJL_ERR_UNSUPPORTED, "mjl_geom_distance: geom %d has type %d (plane, sphere and capsule have closed forms)",
+                  g, d.geom_type[g]);
+  DistArgs A;
+  A.m = B->d_model; A.tab = B->d_dyntab; A.qpos = B->s.qpos; A.mask = mask;
+  A.nenv = B->nenv; A.npair = npair;
+  A.chunk = B->dist_chunk > 0 ? B->dist_chunk : kDistChunk;
+  A.nchunk = (npair + A.chunk - 1) / A.chunk;
+  A.geom1 = geom1; A.geom2 = geom2; A.distmax = distmax;
+  A.dist = dist; A.fromto = fromto; A.normal = normal; A.jac = jac;
+  const long long blocks = (long long)B->nenv * A.nchunk;
+  if (blocks > 0x7fffffffLL)
+    return fail(MJL_ERR_ARG, "mjl_geom_distance: %d envs x %d pair chunks exceed one launch", B->nenv, A.nchunk);
+  HIPCHK(hipSetDevice(B->device));
+  hipLaunchKernelGGL(geom_distance_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, A);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
 }
 
 int mjl_step(mjlBatch* B, const float* ctrl, void* stream) {

@@ -10,6 +10,7 @@ done flags are exactly those of the reference's merge.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
@@ -275,6 +276,27 @@ class HumanoidEnv:
                           torch.zeros((n, r, 3), device=dev)))
         dlp, dlv, out = bufs[key]
         return ray_scan(self.sys, self.data, frame, dlp, dlv, align, flg_static, bodyexclude, cutoff, mask, out)
+
+    def geom_distance(self, geom1, geom2, distmax: float = math.inf, with_jac: bool = False,
+                      mask: Optional[torch.Tensor] = None):
+        """Signed geom distances of the envs' current state (mjx.geom_distance): GeomDistance(dist, fromto, normal,
+        jac) in tensors this env owns. The pairs' device tables and the outputs are allocated (zeros) at the first
+        call with this pair list (jac at the first call that asks for it) and written again by every later one, so
+        after one eager call it is one launch on the post-step state that can be captured with the step, as jac()."""
+        from .mjx import geom_distance, geom_pairs
+        ids1, ids2 = geom_pairs(self.sys, geom1, geom2)
+        key = (tuple(ids1), tuple(ids2))
+        bufs = self.__dict__.setdefault("_distance_bufs", {})
+        dev, n, p = self.obs.device, self.num_envs, len(ids1)
+        if key not in bufs:
+            bufs[key] = [(torch.tensor(ids1, dtype=torch.int32, device=dev), torch.tensor(ids2, dtype=torch.int32, device=dev)),
+                         torch.zeros((n, p), device=dev), torch.zeros((n, p, 6), device=dev),
+                         torch.zeros((n, p, 3), device=dev), None]
+        b = bufs[key]
+        if with_jac and b[4] is None:
+            b[4] = torch.zeros((n, p, self.sys.nv), device=dev)
+        return geom_distance(self.sys, self.data, None, None, distmax, mask, (b[1], b[2], b[3], b[4] if with_jac else None),
+                             _dev=b[0])
 
     def _next_counter(self) -> int:
         self.counter += 1

@@ -14,6 +14,7 @@ return it, and fields are read/written as torch tensors on the batch's GPU.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import NamedTuple, Optional
 
@@ -456,6 +457,143 @@ def ray_scan(sys: Model, d: Data, frame, lpnt, lvec, align: str = "pose", flg_st
                              abi.RAY_STATIC if flg_static else 0, _body_arg(sys, bodyexclude, body), float(cutoff),
                              _ptr(dist), None if geomid is None else _iptr(geomid), _ptr(hitpos), _stream()))
     return dist, geomid, hitpos
+
+
+MAX_DISTANCE_PAIRS = 65535  # mjl_geom_distance's npair
+
+
+class GeomDistance(NamedTuple):
+    dist: torch.Tensor              # [nenv, npair]
+    fromto: Optional[torch.Tensor]  # [nenv, npair, 6]
+    normal: Optional[torch.Tensor]  # [nenv, npair, 3]
+    jac: Optional[torch.Tensor]     # [nenv, npair, nv]
+
+
+class BodyDistance(NamedTuple):
+    dist: torch.Tensor              # [nenv, nquery]
+    fromto: torch.Tensor            # [nenv, nquery, 6]
+    normal: torch.Tensor            # [nenv, nquery, 3]
+    jac: Optional[torch.Tensor]     # [nenv, nquery, nv]
+    geom1: torch.Tensor             # [nenv, nquery] int64: the nearest pair's geom of body1
+    geom2: torch.Tensor             # [nenv, nquery] and of body2
+
+
+def _ids(sys: Model, kind: str, x, n: int) -> list:
+    """Ids of `x` (an id, a name, or a list of either) of object kind "geom" / "body", checked on the host."""
+    ids = []
+    for g in _as_list(x):
+        if isinstance(g, str):
+            i = sys.m.name2id(kind, g)
+            if i < 0:
+                raise ValueError(f"no {kind} named {g!r}")
+        else:
+            i = int(g)
+        if not 0 <= i < n:
+            raise ValueError(f"{kind} id {i} outside 0..{n - 1}")
+        ids.append(i)
+    return ids
+
+
+def geom_pairs(sys: Model, geom1, geom2):
+    """(ids1, ids2) of geom_distance's pairs: geom1 / geom2 are ids or names, scalars or equal-length lists. Bad
+    ids or names, equal geoms and plane - plane pairs raise ValueError."""
+    ids1, ids2 = _ids(sys, "geom", geom1, sys.m.ngeom), _ids(sys, "geom", geom2, sys.m.ngeom)
+    if len(ids1) != len(ids2):
+        raise ValueError(f"geom1 has {len(ids1)} entries and geom2 {len(ids2)}")
+    if not 1 <= len(ids1) <= MAX_DISTANCE_PAIRS:
+        raise ValueError(f"geom_distance takes 1..{MAX_DISTANCE_PAIRS} pairs, not {len(ids1)}")
+    gtype = sys.m.arrays["geom_type"]
+    for a, b in zip(ids1, ids2):
+        if a == b:
+            raise ValueError(f"geom {a} is paired with itself")
+        if gtype[a] == mjcf.GEOM_PLANE and gtype[b] == mjcf.GEOM_PLANE:
+            raise ValueError(f"geoms {a} and {b} are both planes: no distance is defined")
+    return ids1, ids2
+
+
+def collision_pairs(sys: Model):
+    """The model's own collision pairs as two geom id lists (the pairs the step tests for contact), so that
+    geom_distance(sys, d, *collision_pairs(sys), distmax=...) is the clearance of everything that can collide."""
+    A = sys.m.arrays
+    return [int(g) for g in A["pair_geom1"]], [int(g) for g in A["pair_geom2"]]
+
+
+def geom_distance(sys: Model, d: Data, geom1, geom2, distmax: float = math.inf, mask: Optional[torch.Tensor] = None,
+                  out=None, with_jac: bool = False, _dev=None) -> GeomDistance:
+    """mj_geomDistance with a leading env axis: GeomDistance(dist [nenv, npair], fromto [nenv, npair, 6], normal
+    [nenv, npair, 3], jac [nenv, npair, nv] or None) of the pairs (geom1[k], geom2[k]): ids or names, scalars or
+    equal-length lists, checked on the host (ValueError). dist is the signed distance of the two surfaces (negative:
+    overlap), fromto[..., :3] lies on geom1 and fromto[..., 3:] on geom2, normal points from geom1 to geom2
+    (to = from + dist normal), jac = normal' (jacp(to) - jacp(from)) is the gradient: jac @ qvel is the rate of dist.
+    A pair further apart than distmax gets dist = distmax and zeros elsewhere. Poses come from the batch's current
+    qpos inside the call: no forward is needed first. Rows of envs with mask <= 0.5 keep what `out` held (fresh
+    tensors are zeros under a mask). out: (dist, fromto, normal, jac) to write into, any but dist may be None
+    (then it is not computed and None comes back for it); without out, jac is computed when with_jac. One launch,
+    capturable when out holds device tensors and the pair tables are cached (HumanoidEnv.geom_distance). See
+    include/mjx355.h mjl_geom_distance."""
+    if _dev is None:
+        ids1, ids2 = geom_pairs(sys, geom1, geom2)
+        _dev = (torch.tensor(ids1, dtype=torch.int32, device=d.device), torch.tensor(ids2, dtype=torch.int32, device=d.device))
+    g1, g2 = _dev
+    n = g1.shape[0]
+    if not float(distmax) > 0.0:
+        raise ValueError(f"distmax must be greater than 0, not {distmax}")
+    shapes = ((d.nenv, n), (d.nenv, n, 6), (d.nenv, n, 3), (d.nenv, n, sys.nv))
+    if out is None:
+        new = torch.zeros if mask is not None else torch.empty
+        out = tuple(new(s, dtype=torch.float32, device=d.device) for s in shapes[:4 if with_jac else 3])
+    out = (tuple(out) + (None, None, None))[:4]
+    if out[0] is None:
+        raise MjlError("geom_distance needs dist")
+    for t, s, what in zip(out, shapes, GeomDistance._fields):
+        if t is not None and (tuple(t.shape) != s or t.device != d.device):
+            raise MjlError(f"{what} must have shape {s} on {d.device}")
+    mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
+    check(lib().mjl_geom_distance(d.handle, _ptr(mk), n, _iptr(g1), _iptr(g2), float(distmax), *(_ptr(t) for t in out),
+                                  _stream()))
+    return GeomDistance(*out)
+
+
+def body_pairs(sys: Model, body1, body2):
+    """The geom pairs behind body_distance's queries: (ids1, ids2, index [nquery, L]) with row k of `index` the
+    positions in the pair lists of every (geom of body1[k], geom of body2[k]) pair, padded to the longest row by
+    repeating its first entry. A body without geoms raises ValueError."""
+    b1, b2 = _ids(sys, "body", body1, sys.nbody), _ids(sys, "body", body2, sys.nbody)
+    if len(b1) != len(b2) or not b1:
+        raise ValueError(f"body1 has {len(b1)} entries and body2 {len(b2)}")
+    gb = sys.m.arrays["geom_bodyid"]
+    ids1, ids2, rows = [], [], []
+    for x, y in zip(b1, b2):
+        ga, gc = [g for g in range(sys.m.ngeom) if gb[g] == x], [g for g in range(sys.m.ngeom) if gb[g] == y]
+        for b, gs in ((x, ga), (y, gc)):
+            if not gs:
+                raise ValueError(f"body {b} has no geoms")
+        rows.append(list(range(len(ids1), len(ids1) + len(ga) * len(gc))))
+        ids1 += [a for a in ga for _ in gc]
+        ids2 += [c for _ in ga for c in gc]
+    ids1, ids2 = geom_pairs(sys, ids1, ids2)
+    L = max(len(r) for r in rows)
+    return ids1, ids2, [r + [r[0]] * (L - len(r)) for r in rows]
+
+
+def body_distance(sys: Model, d: Data, body1, body2, distmax: float = math.inf, mask: Optional[torch.Tensor] = None,
+                  with_jac: bool = False, _dev=None) -> BodyDistance:
+    """The distance sensors' body form: per query (body1[k], body2[k]) (ids or names, scalars or equal-length
+    lists) the smallest geom_distance over all geom pairs of the two bodies, with that pair's fromto, normal and
+    jac and its geom ids (the first such pair in (geom1, geom2) order on a tie, so the first pair when every pair
+    is beyond distmax). One geom_distance launch over all the pairs plus a torch min / gather. Under a mask the
+    rows of the other envs are zeros. A body without geoms raises ValueError."""
+    if _dev is None:
+        ids1, ids2, index = body_pairs(sys, body1, body2)
+        _dev = tuple(torch.tensor(x, dtype=dt, device=d.device)
+                     for x, dt in ((ids1, torch.int32), (ids2, torch.int32), (index, torch.int64)))
+    g1, g2, index = _dev
+    nq, L = index.shape
+    r = geom_distance(sys, d, None, None, distmax, mask, None, with_jac, _dev=(g1, g2))
+    dist, k = r.dist[:, index].min(dim=2)                 # [nenv, nq]
+    win = index.unsqueeze(0).expand(d.nenv, nq, L).gather(2, k.unsqueeze(2)).squeeze(2)  # positions in the pair list
+    pick = lambda t: None if t is None else t.gather(1, win.unsqueeze(2).expand(-1, -1, t.shape[2]))
+    return BodyDistance(dist, pick(r.fromto), pick(r.normal), pick(r.jac), g1.long()[win], g2.long()[win])
 
 
 MAX_JAC_POINTS = 256  # mjl_jac's npoint
