@@ -811,6 +811,54 @@ int mjl_ik(mjlBatch* batch, const float* mask, int ntask, const int32_t* body, c
            const float* qpos_ref, int32_t dofmask, int iterations, float damping, float posture, float max_step,
            float tol, int flags, float* qpos_out, float* err, int32_t* niter, void* stream);
 
+/* Whole-body inverse kinematics: mjl_ik's solve with a centre-of-mass task and one-sided geom-clearance tasks in the
+ * same normal equations, still one launch of one wavefront per env. The arguments up to niter are mjl_ik's, in its
+ * order and with its meaning, except that ntask may be 0 (body, offset, the targets and weight may then be NULL)
+ * provided a CoM task or a pair exists. With com_body = -1 and npair = 0 qpos_out, err and niter are mjl_ik's bit
+ * for bit. The added arguments:
+ *   com_body      -1: no CoM task; 0: the centre of mass of the whole model; b > 0: of the subtree rooted at body b
+ *   com_target    device [nenv, 3], world frame, read at execution time; required with com_body >= 0
+ *   com_weight    HOST [3] or NULL (ones): one weight >= 0 per world axis; a weight that is not > 0 drops that row, so
+ *                 (1, 1, 0) is "the CoM above a point on the ground"
+ *   npair         0..32 clearance pairs; geom1, geom2 HOST int32 [npair]; clear_min HOST [npair], metres, >= 0;
+ *                 clear_weight HOST [npair] or NULL (ones), >= 0. A plane - sphere / capsule pair is allowed (a foot
+ *                 above the floor).
+ *   com_err       device [nenv, 3] or NULL: e_c at the returned qpos_out, zeros in dropped rows and without a CoM task
+ *   clearance     device [nenv, npair] or NULL: the signed dist of every pair at the returned qpos_out, active or not
+ * The five HOST arrays are read by the host during the call and copied into the kernel's arguments (so the host can
+ * refuse them, and a captured launch carries their values); every other pointer is a device pointer as in mjl_ik.
+ * The iteration is mjl_ik's with these additions, all in float32:
+ *   2. Residuals. CoM: with m_k, xipos_k the mass and inertial-frame origin of body k (the env's own masses while
+ *      MJL_OPT_PER_ENV_MODEL is on, as mjl_centroidal), M = sum m_k and c = (sum m_k xipos_k) / M over the bodies of
+ *      the subtree in id order (mjl_centroidal's sums), e_c = com_target - c. Pairs: dist_p, from, to, normal exactly
+ *      as mjl_geom_distance defines them at distmax = +inf (its closed forms and degenerate-case rules), from the
+ *      iterate's frames. Pair p is active iff dist_p < clear_min[p] (strict); its residual is clear_min[p] - dist_p
+ *      when active, else 0. res also takes com_weight[a] |e_c[a]|, a = x, y, z, then clear_weight[p] max(0,
+ *      clear_min[p] - dist_p), p in index order, after the frame tasks' terms.
+ *   4. Normal equations. After the last frame task, with the same chain H[i][j] = fma(c[i], c[j], H[i][j]),
+ *      g[i] = fma(c[i], w e, g[i]): the CoM rows a = x, y, z that are not dropped, c = com_weight[a] * row a of
+ *      mjl_centroidal's jac_com of the subtree, w e = com_weight[a] e_c[a]; then the active pairs with clear_weight
+ *      > 0 in index order, c = clear_weight[p] * (+ mjl_geom_distance's jac row of the pair), w e = clear_weight[p]
+ *      (clear_min[p] - dist_p): the step increases the distance. An inactive pair adds nothing to H or g. Columns of
+ *      dofs outside dofmask are zero, as for the frame rows. H stays symmetric bit for bit.
+ * Steps 1, 3, 5 and 6 are unchanged; the stop test is the same for the whole wavefront. The rows are one-sided, not
+ * a QP: a pair that is inactive at the iterate does not bound the step taken from it.
+ * A body id outside 0..nbody-1 in a frame task gives NaN rows in qpos_out, err, com_err and clearance and niter = 0.
+ * mask, "nothing of the batch is written", no allocation, no synchronisation and capturability as mjl_ik.
+ * MJL_ERR_ARG, before anything touches the device: mjl_ik's refusals (ntask outside 0..32; body or both targets NULL
+ * only with ntask > 0); no task of any kind; com_body outside -1..nbody-1; com_target NULL with com_body >= 0; npair
+ * outside 0..32; geom1, geom2 or clear_min NULL with npair > 0; a geom id outside 0..ngeom-1, a geom paired with
+ * itself, a plane - plane pair (mjl_geom_distance's rules, checked on the host here); a negative or non-finite
+ * com_weight, clear_weight or clear_min.
+ * MJL_ERR_UNSUPPORTED: npair > 0 on a model with a geom that is no plane, sphere or capsule. */
+int mjl_ik_wb(mjlBatch* batch, const float* mask, int ntask, const int32_t* body, const float* offset,
+              const float* target_pos, const float* target_quat, const float* weight, const float* qpos_start,
+              const float* qpos_ref, int32_t dofmask, int iterations, float damping, float posture, float max_step,
+              float tol, int flags, float* qpos_out, float* err, int32_t* niter, int com_body,
+              const float* com_target, const float* com_weight, int npair, const int32_t* geom1,
+              const int32_t* geom2, const float* clear_min, const float* clear_weight, float* com_err,
+              float* clearance, void* stream);
+
 /* The persistent per-env state (what a step reads and writes: Data.qpos, qvel, qacc_warmstart,
  * time, plus the env aux) as packed rows [nenv, mjl_state_size] = [qpos | qvel | qacc_warmstart |
  * aux | time]: the APG remat tape entry (train_apg.py:187-189 checkpoints each step's carry).

@@ -735,7 +735,30 @@ int mjl_centroidal(mjlBatch* B, const float* mask, int nsub, const int32_t* body
   return MJL_OK;
 }
 
-// One launch (ik_kernels.hip): every iteration of every env's solve on chip, nothing of the batch written.
+// One launch each (ik_kernels.hip): every iteration of every env's solve on chip, nothing of the batch written.
+// The checks of the scalars mjl_ik and mjl_ik_wb share (fn: the entry's name in the message).
+static int ik_check_scalars(const char* fn, int iterations, float damping, float posture, float max_step, float tol,
+                            int flags) {
+  if (iterations < 0 || iterations > 1024) return fail(MJL_ERR_ARG, "%s: iterations = %d outside 0..1024", fn, iterations);
+  if (!(damping > 0.f) || !std::isfinite(damping)) return fail(MJL_ERR_ARG, "%s: damping = %g: a finite value > 0", fn, damping);
+  if (!(posture >= 0.f) || !std::isfinite(posture)) return fail(MJL_ERR_ARG, "%s: posture = %g: a finite value >= 0", fn, posture);
+  if (!(max_step >= 0.f) || !std::isfinite(max_step)) return fail(MJL_ERR_ARG, "%s: max_step = %g: a finite value >= 0", fn, max_step);
+  if (!(tol >= 0.f) || !std::isfinite(tol)) return fail(MJL_ERR_ARG, "%s: tol = %g: a finite value >= 0", fn, tol);
+  if (flags & ~MJL_IK_LIMITS) return fail(MJL_ERR_ARG, "%s: flags = %d: 0 or MJL_IK_LIMITS", fn, flags);
+  return MJL_OK;
+}
+
+static void ik_fill(IkArgs& A, mjlBatch* B, const float* mask, int ntask, const int32_t* body, const float* offset,
+                    const float* target_pos, const float* target_quat, const float* weight, const float* qpos_start,
+                    const float* qpos_ref, int32_t dofmask, int iterations, float damping, float posture,
+                    float max_step, float tol, int flags, float* qpos_out, float* err, int32_t* niter) {
+  A.m = B->d_model; A.tab = B->d_dyntab; A.qstart = qpos_start ? qpos_start : B->s.qpos; A.qref = qpos_ref;
+  A.mask = mask; A.nenv = B->nenv; A.ntask = ntask; A.body = body; A.offset = offset; A.tpos = target_pos;
+  A.tquat = target_quat; A.weight = weight; A.dofmask = (uint32_t)dofmask; A.iterations = iterations;
+  A.limits = (flags & MJL_IK_LIMITS) != 0; A.damping = damping; A.posture = posture; A.max_step = max_step; A.tol = tol;
+  A.qout = qpos_out; A.err = err; A.niter = niter;
+}
+
 int mjl_ik(mjlBatch* B, const float* mask, int ntask, const int32_t* body, const float* offset, const float* target_pos,
            const float* target_quat, const float* weight, const float* qpos_start, const float* qpos_ref,
            int32_t dofmask, int iterations, float damping, float posture, float max_step, float tol, int flags,
@@ -745,20 +768,73 @@ int mjl_ik(mjlBatch* B, const float* mask, int ntask, const int32_t* body, const
   if (!qpos_out) return fail(MJL_ERR_ARG, "mjl_ik: qpos_out is required");
   if (ntask < 1 || ntask > kIkMaxTask) return fail(MJL_ERR_ARG, "mjl_ik: ntask = %d outside 1..%d", ntask, kIkMaxTask);
   if (!target_pos && !target_quat) return fail(MJL_ERR_ARG, "mjl_ik: target_pos and target_quat are both NULL");
-  if (iterations < 0 || iterations > 1024) return fail(MJL_ERR_ARG, "mjl_ik: iterations = %d outside 0..1024", iterations);
-  if (!(damping > 0.f) || !std::isfinite(damping)) return fail(MJL_ERR_ARG, "mjl_ik: damping = %g: a finite value > 0", damping);
-  if (!(posture >= 0.f) || !std::isfinite(posture)) return fail(MJL_ERR_ARG, "mjl_ik: posture = %g: a finite value >= 0", posture);
-  if (!(max_step >= 0.f) || !std::isfinite(max_step)) return fail(MJL_ERR_ARG, "mjl_ik: max_step = %g: a finite value >= 0", max_step);
-  if (!(tol >= 0.f) || !std::isfinite(tol)) return fail(MJL_ERR_ARG, "mjl_ik: tol = %g: a finite value >= 0", tol);
-  if (flags & ~MJL_IK_LIMITS) return fail(MJL_ERR_ARG, "mjl_ik: flags = %d: 0 or MJL_IK_LIMITS", flags);
+  if (int rc = ik_check_scalars("mjl_ik", iterations, damping, posture, max_step, tol, flags)) return rc;
   HIPCHK(hipSetDevice(B->device));
   IkArgs A;
-  A.m = B->d_model; A.tab = B->d_dyntab; A.qstart = qpos_start ? qpos_start : B->s.qpos; A.qref = qpos_ref;
-  A.mask = mask; A.nenv = B->nenv; A.ntask = ntask; A.body = body; A.offset = offset; A.tpos = target_pos;
-  A.tquat = target_quat; A.weight = weight; A.dofmask = (uint32_t)dofmask; A.iterations = iterations;
-  A.limits = (flags & MJL_IK_LIMITS) != 0; A.damping = damping; A.posture = posture; A.max_step = max_step; A.tol = tol;
-  A.qout = qpos_out; A.err = err; A.niter = niter;
-  hipLaunchKernelGGL(ik_kernel, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
+  ik_fill(A, B, mask, ntask, body, offset, target_pos, target_quat, weight, qpos_start, qpos_ref, dofmask, iterations,
+          damping, posture, max_step, tol, flags, qpos_out, err, niter);
+  hipLaunchKernelGGL(ik_kernel<false>, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
+  HIPCHK(hipGetLastError());
+  return MJL_OK;
+}
+
+int mjl_ik_wb(mjlBatch* B, const float* mask, int ntask, const int32_t* body, const float* offset,
+              const float* target_pos, const float* target_quat, const float* weight, const float* qpos_start,
+              const float* qpos_ref, int32_t dofmask, int iterations, float damping, float posture, float max_step,
+              float tol, int flags, float* qpos_out, float* err, int32_t* niter, int com_body, const float* com_target,
+              const float* com_weight, int npair, const int32_t* geom1, const int32_t* geom2, const float* clear_min,
+              const float* clear_weight, float* com_err, float* clearance, void* stream) {
+  if (!B) return fail(MJL_ERR_ARG, "null batch");
+  if (!qpos_out) return fail(MJL_ERR_ARG, "mjl_ik_wb: qpos_out is required");
+  if (ntask < 0 || ntask > kIkMaxTask) return fail(MJL_ERR_ARG, "mjl_ik_wb: ntask = %d outside 0..%d", ntask, kIkMaxTask);
+  if (ntask > 0 && !body) return fail(MJL_ERR_ARG, "mjl_ik_wb: body is required with ntask > 0");
+  if (ntask > 0 && !target_pos && !target_quat)
+    return fail(MJL_ERR_ARG, "mjl_ik_wb: target_pos and target_quat are both NULL with ntask > 0");
+  if (int rc = ik_check_scalars("mjl_ik_wb", iterations, damping, posture, max_step, tol, flags)) return rc;
+  const mjlModelDesc& d = B->model->desc;
+  if (com_body < -1 || com_body >= d.nbody)
+    return fail(MJL_ERR_ARG, "mjl_ik_wb: com_body = %d outside -1..%d", com_body, d.nbody - 1);
+  if (com_body >= 0 && !com_target) return fail(MJL_ERR_ARG, "mjl_ik_wb: com_target is required with com_body >= 0");
+  if (npair < 0 || npair > kIkMaxPair) return fail(MJL_ERR_ARG, "mjl_ik_wb: npair = %d outside 0..%d", npair, kIkMaxPair);
+  if (ntask == 0 && com_body < 0 && npair == 0) return fail(MJL_ERR_ARG, "mjl_ik_wb: no task of any kind");
+  if (npair > 0 && (!geom1 || !geom2 || !clear_min))
+    return fail(MJL_ERR_ARG, "mjl_ik_wb: geom1, geom2 and clear_min are required with npair > 0");
+  IkWbArgs A;
+  for (int i = 0; i < 3; i++) {
+    const float w = com_weight ? com_weight[i] : 1.f;
+    if (com_body >= 0 && (!(w >= 0.f) || !std::isfinite(w)))
+      return fail(MJL_ERR_ARG, "mjl_ik_wb: com_weight[%d] = %g: a finite value >= 0", i, w);
+    A.com_weight[i] = w;
+  }
+  for (int p = 0; p < kIkMaxPair; p++) {
+    A.geom1[p] = A.geom2[p] = 0;
+    A.clear_min[p] = A.clear_weight[p] = 0.f;
+  }
+  if (npair > 0)
+    for (int g = 0; g < d.ngeom; g++)
+      if (d.geom_type[g] != MJL_GEOM_PLANE && d.geom_type[g] != MJL_GEOM_SPHERE && d.geom_type[g] != MJL_GEOM_CAPSULE)
+        return fail(MJL_ERR_UNSUPPORTED, "mjl_ik_wb: geom %d has type %d (plane, sphere and capsule have closed forms)",
+                    g, d.geom_type[g]);
+  for (int p = 0; p < npair; p++) {
+    const int g1 = geom1[p], g2 = geom2[p];
+    const int ng = d.ngeom < MJL_MAXGEOM ? d.ngeom : MJL_MAXGEOM;
+    if (g1 < 0 || g1 >= ng || g2 < 0 || g2 >= ng)
+      return fail(MJL_ERR_ARG, "mjl_ik_wb: pair %d: geoms %d, %d outside 0..%d", p, g1, g2, ng - 1);
+    if (g1 == g2) return fail(MJL_ERR_ARG, "mjl_ik_wb: pair %d: geom %d is paired with itself", p, g1);
+    if (d.geom_type[g1] == MJL_GEOM_PLANE && d.geom_type[g2] == MJL_GEOM_PLANE)
+      return fail(MJL_ERR_ARG, "mjl_ik_wb: pair %d: geoms %d and %d are both planes", p, g1, g2);
+    const float w = clear_weight ? clear_weight[p] : 1.f;
+    if (!(w >= 0.f) || !std::isfinite(w)) return fail(MJL_ERR_ARG, "mjl_ik_wb: clear_weight[%d] = %g: a finite value >= 0", p, w);
+    if (!(clear_min[p] >= 0.f) || !std::isfinite(clear_min[p]))
+      return fail(MJL_ERR_ARG, "mjl_ik_wb: clear_min[%d] = %g: a finite value >= 0", p, clear_min[p]);
+    A.geom1[p] = (uint8_t)g1; A.geom2[p] = (uint8_t)g2; A.clear_min[p] = clear_min[p]; A.clear_weight[p] = w;
+  }
+  HIPCHK(hipSetDevice(B->device));
+  ik_fill(A, B, mask, ntask, body, offset, target_pos, target_quat, weight, qpos_start, qpos_ref, dofmask, iterations,
+          damping, posture, max_step, tol, flags, qpos_out, err, niter);
+  A.m_env = B->d_model_env; A.com_target = com_target; A.com_body = com_body; A.npair = npair;
+  A.com_err = com_err; A.clearance = clearance;
+  hipLaunchKernelGGL(ik_kernel<true>, dim3(B->nenv), dim3(64), 0, (hipStream_t)stream, A);
   HIPCHK(hipGetLastError());
   return MJL_OK;
 }

@@ -21,8 +21,29 @@
 //   6. dq into LDS; lane = dof: a hinge or a free translation adds its entry (a limited hinge is clamped), the lane
 //      of a free joint's first rotation dof advances the quaternion (unless its three entries of dq are zero).
 // After the loop the residual stage holds e at the returned iterate: err is stored from it, qpos_out from the iterate.
+//
+// ik_kernel<true> (mjl_ik_wb) is the same iteration with a centre-of-mass task and one-sided clearance rows, each
+// phase behind `if constexpr (WB)`, so ik_kernel<false> (mjl_ik) is the kernel above, instruction for instruction:
+//   2a. (a CoM task) lane = body: xipos and the env's own mass into LDS; lane = subtree root: its mass and centre of
+//       mass (cent_subtree_com, centroidal_dev.h). e_c = com_target - centre of mass of com_body, the same in every
+//       lane; res takes com_weight[a] |e_c[a]|.
+//   2b. (npair > 0) lane = geom: the scene record (scene_geom_record, ray_kernels.hip) and its body into LDS;
+//       lane = pair: dist_pair (distance_dev.h), the pair's witness points, normal and bodies into the pair stage,
+//       dist and the residual clear_min - dist in the lane's registers; a pair with dist < clear_min is active; res
+//       takes clear_weight max(0, clear_min - dist) by readlane, in pair order.
+//   4a. after the frame tasks, the CoM rows: column d of jac_com (cent_column) times com_weight into rows 0..2 of
+//       the stage Js, then the same fma chain as a frame task's position rows, x, y, z.
+//   4b. then the active pairs in index order (a scalar branch on the pair's weight, read by readlane): lane d's entry
+//       of the gradient row (dist_jac_entry) times clear_weight into row 0 of Js, one more pass of the chain.
+// After the loop com_err is stored from e_c and clearance from the pair lanes' dist. 3840 B more LDS, whatever npair.
 // Included by capi.hip after dyn_kernels.hip.
 #pragma once
+
+#include <type_traits>
+
+#include "centroidal_dev.h"
+#include "distance_dev.h"
+#include "ray_kernels.hip"
 
 namespace mjl {
 
@@ -47,6 +68,20 @@ struct IkArgs {
 };
 
 constexpr int kIkMaxTask = 32;
+constexpr int kIkMaxPair = 32;
+
+// mjl_ik_wb: IkArgs and the whole-body tasks. The small tables are host arrays copied into the kernel arguments.
+struct IkWbArgs : IkArgs {
+  const ModelF* m_env;    // [nenv] per-env blocks (the masses of the CoM task), or null
+  const float* com_target;  // [nenv, 3] or null (no CoM task)
+  int com_body;           // -1: no CoM task
+  int npair;
+  float com_weight[3];    // <= 0: the row is dropped
+  uint8_t geom1[kIkMaxPair], geom2[kIkMaxPair];
+  float clear_min[kIkMaxPair], clear_weight[kIkMaxPair];
+  float* com_err;         // [nenv, 3] or null
+  float* clearance;       // [nenv, npair] or null
+};
 
 // the rotation vector of the unit quaternion q (its scalar part made non-negative): mju_quat2Vel at dt = 1
 static INL void ik_rotvec(float* r, const float* q) {
@@ -57,7 +92,8 @@ static INL void ik_rotvec(float* r, const float* q) {
   for (int i = 0; i < 3; i++) r[i] = v[i] * s;
 }
 
-__global__ __launch_bounds__(64) void ik_kernel(IkArgs A) {
+template <bool WB>
+__global__ __launch_bounds__(64) void ik_kernel(std::conditional_t<WB, IkWbArgs, IkArgs> A) {
   constexpr int NV = MJL_MAXV, LD = kDynLD;
   __shared__ float qpos[MJL_MAXQ], qref[MJL_MAXQ];
   __shared__ float xpos[MJL_MAXBODY][3], xquat[MJL_MAXBODY][4];
@@ -67,6 +103,15 @@ __global__ __launch_bounds__(64) void ik_kernel(IkArgs A) {
   __shared__ __attribute__((aligned(16))) float Js[6][NV];  // one task's weighted Jacobian rows
   __shared__ float dqs[NV];
   __shared__ float Ms[NV * LD];          // L's rows in for its columns
+  // The whole-body tasks' workspace. ik_kernel<false> declares one element of each and never names it (every use
+  // stands in an `if constexpr (WB)` block), so the compiler drops them: mjl_ik's 8320 B of LDS rest on that
+  // elimination. `make resource-usage` shows it; a use outside those blocks would grow mjl_ik's LDS.
+  __shared__ float xim[WB ? MJL_MAXBODY : 1][4];  // xipos, mass
+  __shared__ float cm[WB ? MJL_MAXBODY : 1][4];   // subtree: centre of mass, mass
+  __shared__ int ssend[WB ? MJL_MAXBODY : 1];
+  __shared__ f32x4 S4[WB ? 2 * MJL_MAXGEOM : 1];  // the geoms' scene records
+  __shared__ int gbody[WB ? MJL_MAXGEOM : 1];
+  __shared__ float P[WB ? kIkMaxPair * kDistStage : 1];  // the pairs' witness points, normals and bodies
   const int env = blockIdx.x, lane = threadIdx.x;
   if (env >= A.nenv) return;
   if (A.mask && !(A.mask[env] > 0.5f)) return;
@@ -85,6 +130,10 @@ __global__ __launch_bounds__(64) void ik_kernel(IkArgs A) {
     if (A.err)
       for (int i = lane; i < ntask * 6; i += 64) A.err[(size_t)env * ntask * 6 + i] = nan;
     if (A.niter && lane == 0) A.niter[env] = 0;
+    if constexpr (WB) {
+      if (A.com_err && lane < 3) A.com_err[(size_t)env * 3 + lane] = nan;
+      if (A.clearance && lane < A.npair) A.clearance[(size_t)env * A.npair + lane] = nan;
+    }
     return;
   }
 
@@ -137,6 +186,36 @@ __global__ __launch_bounds__(64) void ik_kernel(IkArgs A) {
   }
   const float diag0 = A.damping + A.posture;
 
+  // ---- the whole-body tasks' constants (WB): lane = body its own mass, lane = pair the pair's record
+  [[maybe_unused]] bool hascom = false, ispair = false;
+  [[maybe_unused]] float bmass = 0.f, bipos[3] = {0.f, 0.f, 0.f}, cw[3] = {0.f, 0.f, 0.f}, ct[3] = {0.f, 0.f, 0.f};
+  [[maybe_unused]] float ec[3] = {0.f, 0.f, 0.f}, pcmin = 0.f, pcw = 0.f, pdist = 0.f, pres = 0.f, pwact = 0.f;
+  [[maybe_unused]] int pg1 = 0, pg2 = 0, send = 0, db = 0, ngeom = 0;
+  if constexpr (WB) {
+    hascom = A.com_body >= 0 && A.com_body < nbody;
+    if (hascom) {
+      const MP me = uniform_ptr((MP)(A.m_env ? A.m_env + env : A.m));  // the env's own masses
+      if (lane > 0 && lane < nbody) {
+        bmass = me->brec[lane].mass;
+        for (int i = 0; i < 3; i++) bipos[i] = me->brec[lane].ipos[i];
+      }
+      for (int i = 0; i < 3; i++) {
+        cw[i] = A.com_weight[i] > 0.f ? A.com_weight[i] : 0.f;
+        ct[i] = A.com_target[(size_t)env * 3 + i];
+      }
+      send = lane < nbody ? max(lane + 1, min(br.subtree_end, nbody)) : 0;
+      db = max(0, min(dr.bodyid, nbody - 1));
+    }
+    ngeom = min(m->ngeom, MJL_MAXGEOM);
+    ispair = lane < A.npair;
+    if (ispair) {
+      pg1 = min((int)A.geom1[lane], ngeom - 1);
+      pg2 = min((int)A.geom2[lane], ngeom - 1);
+      pcmin = A.clear_min[lane];
+      pcw = A.clear_weight[lane] > 0.f ? A.clear_weight[lane] : 0.f;
+    }
+  }
+
   int k = 0;
   for (;; k++) {
     dyn_tree_pass(m, br, qpos, xpos, xquat, dax, danc, nbody, maxlevel, lane);
@@ -164,6 +243,61 @@ __global__ __launch_bounds__(64) void ik_kernel(IkArgs A) {
     }
     float res = 0.f;
     for (int t = 0; t < ntask; t++) res = fmaxf(res, rdlane(resl, t));
+    if constexpr (WB) {
+      if (hascom) {  // ---- lane = body: xipos, mass; lane = subtree root: its mass and centre of mass
+        float xi[3] = {0.f, 0.f, 0.f};
+        if (lane > 0 && lane < nbody) {
+          float R[9], dd[3];
+          q2m(R, xquat[lane]);
+          mv3(dd, R, bipos);
+          for (int i = 0; i < 3; i++) xi[i] = xpos[lane][i] + dd[i];
+        }
+        if (lane < nbody) {
+          for (int i = 0; i < 3; i++) xim[lane][i] = xi[i];
+          xim[lane][3] = bmass;
+          ssend[lane] = send;
+        }
+        __syncthreads();
+        if (lane < nbody) {
+          float ms, inv, c[3];
+          bool empty;
+          cent_subtree_com(xim, lane, send, xi, c, ms, inv, empty);
+          for (int i = 0; i < 3; i++) cm[lane][i] = c[i];
+          cm[lane][3] = empty ? 0.f : ms;
+        }
+        __syncthreads();
+        for (int i = 0; i < 3; i++) {
+          ec[i] = cw[i] > 0.f ? ct[i] - cm[A.com_body][i] : 0.f;
+          res = fmaxf(res, cw[i] * fabsf(ec[i]));
+        }
+      }
+      if (A.npair > 0) {  // ---- lane = geom: the scene record and the body; lane = pair: the distance
+        if (lane < ngeom) {
+          const FrameRec fr = ldrec(&m->frec[lane]);
+          const int gb = max(0, min(fr.body, nbody - 1));
+          float gm[9], rec[8];
+          q2m(gm, xquat[gb]);
+          scene_geom_record(m, lane, fr, gm, xpos[gb], rec);
+          S4[2 * lane] = f32x4{rec[0], rec[1], rec[2], rec[3]};
+          S4[2 * lane + 1] = f32x4{rec[4], rec[5], rec[6], rec[7]};
+          gbody[lane] = gb;
+        }
+        __syncthreads();
+        if (ispair) {
+          float from[3], to[3], n[3];
+          pdist = dist_pair(S4[2 * pg1], S4[2 * pg1 + 1], S4[2 * pg2], S4[2 * pg2 + 1], from, to, n);
+          const bool on = pdist < pcmin;
+          pres = on ? pcmin - pdist : 0.f;
+          pwact = on ? pcw : 0.f;
+          float* s = P + lane * kDistStage;
+          for (int i = 0; i < 3; i++) { s[i] = from[i]; s[3 + i] = to[i]; s[6 + i] = n[i]; }
+          s[9] = __int_as_float(gbody[pg1]);
+          s[10] = __int_as_float(gbody[pg2]);
+          s[11] = 1.f;
+        }
+        for (int p = 0; p < A.npair; p++) res = fmaxf(res, rdlane(pwact, p) * rdlane(pres, p));
+      }
+    }
     __syncthreads();
     const bool stop = k >= A.iterations || (A.tol > 0.f && res < A.tol);
     if (__builtin_amdgcn_readfirstlane((int)stop)) break;
@@ -231,6 +365,39 @@ __global__ __launch_bounds__(64) void ik_kernel(IkArgs A) {
       __syncthreads();
     }
 
+    if constexpr (WB) {
+      if (hascom) {  // ---- the CoM rows x, y, z: column d of jac_com, weighted
+        const int S = cent_moved_set(A.tab, A.com_body, d, db, ssend, active);
+        float jc[3], c[3];
+        cent_column<false>(S, A.com_body, cm, nullptr, kind, ax, an, jc, nullptr);
+        for (int i = 0; i < 3; i++) c[i] = cw[i] * jc[i];
+        if (lane < NV)
+          for (int i = 0; i < 3; i++) Js[i][lane] = c[i];
+        __syncthreads();
+#pragma unroll 1
+        for (int r = 0; r < 3; r++) {
+          if (!(cw[r] > 0.f)) continue;
+          const float cr = r == 0 ? c[0] : (r == 1 ? c[1] : c[2]);
+#pragma unroll
+          for (int j = 0; j < NV; j++) a[j] = fmaf(cr, Js[r][j], a[j]);
+          g = fmaf(cr, cw[r] * ec[r], g);
+        }
+        __syncthreads();
+      }
+#pragma unroll 1
+      for (int p = 0; p < A.npair; p++) {  // ---- the active pairs: +w jac, residual w (clear_min - dist)
+        const float w = rdlane(pwact, p), e = rdlane(pres, p);
+        if (!(w > 0.f)) continue;
+        const float c = active ? w * dist_jac_entry(A.tab, P + p * kDistStage, d, kind, ax, an) : 0.f;
+        if (lane < NV) Js[0][lane] = c;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < NV; j++) a[j] = fmaf(c, Js[0][j], a[j]);
+        g = fmaf(c, w * e, g);
+        __syncthreads();
+      }
+    }
+
     // ---- H = L L' (mass_matrix_kernel's factor), the columns of L through the stage, H dq = g
     float invd = 1.f;
 #pragma unroll
@@ -295,6 +462,10 @@ __global__ __launch_bounds__(64) void ik_kernel(IkArgs A) {
   if (A.err)
     for (int i = lane; i < ntask * 6; i += 64) A.err[(size_t)env * ntask * 6 + i] = es[i];
   if (A.niter && lane == 0) A.niter[env] = k;
+  if constexpr (WB) {
+    if (A.com_err && lane < 3) A.com_err[(size_t)env * 3 + lane] = lane == 0 ? ec[0] : (lane == 1 ? ec[1] : ec[2]);
+    if (A.clearance && ispair) A.clearance[(size_t)env * A.npair + lane] = pdist;
+  }
 }
 
 }  // namespace mjl

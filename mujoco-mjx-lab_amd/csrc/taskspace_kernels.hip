@@ -29,8 +29,11 @@
 // A body id outside 0..nbody-1 gives NaN rows. An output passed as NULL costs neither its staging nor its stores
 // (branches on the kernel arguments, uniform over the wave). Every value is stored through x + 0: with qvel = 0
 // the rates are +0 bit for bit.
+// The subtree sums and the columns are centroidal_dev.h's (the whole-body IK kernel runs them too).
 // Included by capi.hip after dyn_kernels.hip (dyn_dof_axis, dyn_emit).
 #pragma once
+
+#include "centroidal_dev.h"
 
 namespace mjl {
 
@@ -311,16 +314,9 @@ __global__ __launch_bounds__(64) void centroidal_kernel(CentArgs A) {
 
   // ---- lane = subtree root s: the composite of [s, subtree_end) about its own centre of mass, and its bias
   if (lane < nbody) {
-    float ms = 0.f, s[3] = {0.f, 0.f, 0.f};
-    for (int k = lane; k < send; k++) {
-      const float mk = xim[k][3];
-      ms += mk;
-      for (int i = 0; i < 3; i++) s[i] += mk * xim[k][i];
-    }
-    const bool empty = ms < kMinVal;  // a massless subtree: its own xipos, zero rows
-    const float inv = empty ? 0.f : 1.f / ms;
-    float c[3];
-    for (int i = 0; i < 3; i++) c[i] = empty ? xi[i] : s[i] * inv;
+    float ms, inv, c[3];
+    bool empty;  // a massless subtree: its own xipos, zero rows
+    cent_subtree_com(xim, lane, send, xi, c, ms, inv, empty);
     float I6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, F[3] = {0.f, 0.f, 0.f}, T[3] = {0.f, 0.f, 0.f};
     for (int k = lane; k < send; k++) {
       const float mk = xim[k][3];
@@ -368,31 +364,9 @@ __global__ __launch_bounds__(64) void centroidal_kernel(CentArgs A) {
     const bool bad = b < 0 || b >= nbody;
     const int bs = bad ? 0 : b;
     // the bodies of S(bs) that dof d moves: all of it, the subtree of the dof's body, or none
-    int S = -1;
-    if (isd) {
-      if ((A.tab->body_dofmask[bs] >> d) & 1u) S = bs;
-      else if (db > bs && db < ssend[bs]) S = db;
-    }
-    const float mb = cm[bs][3];
-    float jc[3] = {0.f, 0.f, 0.f}, am[3] = {0.f, 0.f, 0.f};
-    if (S >= 0 && mb > 0.f) {
-      const float mS = cm[S][3], k = mS / mb;
-      const float cS[3] = {cm[S][0], cm[S][1], cm[S][2]};
-      const float dc[3] = {cS[0] - cm[bs][0], cS[1] - cm[bs][1], cS[2] - cm[bs][2]};
-      float t[3] = {ax[0], ax[1], ax[2]};  // the velocity of the set's centre of mass per unit rate
-      if (kind == 0) {
-        const float r[3] = {cS[0] - an[0], cS[1] - an[1], cS[2] - an[2]};
-        t[0] = t[1] = t[2] = 0.f;
-        add_cross(t, ax, r);
-        const float* I = cI[S];
-        am[0] = I[0] * ax[0] + I[3] * ax[1] + I[4] * ax[2];
-        am[1] = I[3] * ax[0] + I[1] * ax[1] + I[5] * ax[2];
-        am[2] = I[4] * ax[0] + I[5] * ax[1] + I[2] * ax[2];
-      }
-      const float mt[3] = {mS * t[0], mS * t[1], mS * t[2]};
-      add_cross(am, dc, mt);
-      for (int i = 0; i < 3; i++) jc[i] = k * t[i];
-    }
+    const int S = cent_moved_set(A.tab, bs, d, db, ssend, isd);
+    float jc[3], am[3];
+    cent_column<true>(S, bs, cm, cI, kind, ax, an, jc, am);
     for (int i = 0; i < 3; i++) { jc[i] += 0.f; am[i] += 0.f; }
     if (bad)
       for (int i = 0; i < 3; i++) jc[i] = am[i] = nan;

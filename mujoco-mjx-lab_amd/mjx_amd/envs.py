@@ -190,6 +190,33 @@ class HumanoidEnv:
         return ik(self.sys, self.data, frames, target_pos, target_quat, offset, weight, qpos_start, qpos_ref, dofs,
                   iterations, damping, posture, max_step, tol, limits, mask, out, _dev=tabs)
 
+    def ik_wb(self, frames=None, target_pos=None, target_quat=None, *, com_target=None, com_body=0, com_weight=None,
+              clearance=None, clearance_min=0.0, clearance_weight=None, offset=None, weight=None, qpos_start=None,
+              qpos_ref=None, dofs=None, iterations: int = 20, damping: float = 1e-3, posture: float = 0.0,
+              max_step: float = 0.0, tol: float = 0.0, limits: bool = True, mask: Optional[torch.Tensor] = None):
+        """Whole-body inverse kinematics from the envs' current qpos (mjx.ik_wb): WBIKResult(qpos, err, niter,
+        com_err, clearance) in tensors this env owns, allocated (zeros) with the frame tasks' device tables at the
+        first call with these tasks and written again by every later one. The CoM and clearance tables are host
+        values that travel in the launch itself; com_target and the frame targets given as device tensors are read
+        at execution time. After one eager call it is one launch that writes nothing of the envs' state and can be
+        captured with the step, as ik()."""
+        from .mjx import ik_tables, ik_wb, ik_wb_tables
+        ft = (None, None, None, None) if frames is None else ik_tables(self.sys, frames, offset, weight)
+        wb = ik_wb_tables(self.sys, com_body, com_weight, clearance, clearance_min, clearance_weight)
+        key = tuple(None if x is None else (x.tobytes() if hasattr(x, "tobytes") else tuple(x)) for x in ft + wb[1:]) + (wb[0],)
+        bufs = self.__dict__.setdefault("_ik_wb_bufs", {})
+        if key not in bufs:
+            dev, n, p = self.obs.device, self.num_envs, 0 if ft[0] is None else len(ft[0])
+            tabs = (None if ft[0] is None else torch.tensor(ft[0], dtype=torch.int32, device=dev),) + tuple(
+                None if x is None else torch.tensor(x, device=dev) for x in ft[1:])
+            bufs[key] = (tabs, (torch.zeros((n, self.sys.nq), device=dev), torch.zeros((n, p, 6), device=dev),
+                                torch.zeros((n,), dtype=torch.int32, device=dev), torch.zeros((n, 3), device=dev),
+                                torch.zeros((n, len(wb[2])), device=dev)))
+        tabs, out = bufs[key]
+        return ik_wb(self.sys, self.data, frames, target_pos, target_quat, com_target=com_target, qpos_start=qpos_start,
+                     qpos_ref=qpos_ref, dofs=dofs, iterations=iterations, damping=damping, posture=posture,
+                     max_step=max_step, tol=tol, limits=limits, mask=mask, out=out, _dev=(tabs, wb))
+
     def jac_dot(self, frames, offset=None, mask: Optional[torch.Tensor] = None):
         """Time derivatives of jac()'s Jacobians and the velocity-product term (mjx.jac_dot_local): (jacp_dot,
         jacr_dot, jdotv) in tensors this env owns, allocated (zeros) at the first call with these (frames,

@@ -1123,6 +1123,128 @@ def ik(sys: Model, d: Data, frame, target_pos=None, target_quat=None, offset=Non
     return IKResult(qo, eo, no)
 
 
+MAX_IK_PAIRS = 32  # mjl_ik_wb's npair
+
+
+class WBIKResult(NamedTuple):
+    """What `ik_wb` returns: IKResult's fields, the CoM residual and the pairs' signed distances at the solution."""
+    qpos: torch.Tensor                 # [nenv, nq]
+    err: Optional[torch.Tensor]        # [nenv, ntask, 6]
+    niter: Optional[torch.Tensor]      # [nenv] int32
+    com_err: Optional[torch.Tensor]    # [nenv, 3]: com_target - CoM, zeros in dropped rows
+    clearance: Optional[torch.Tensor]  # [nenv, npair]: the signed distance of every pair
+
+
+def ik_wb_tables(sys: Model, com_body=0, com_weight=None, clearance=None, clearance_min=0.0, clearance_weight=None):
+    """Host tables of ik_wb's added tasks, checked here (ValueError): (com body id, com weights float32 [3] or None,
+    geom ids 1, geom ids 2, clear_min float32 [npair], clear weights float32 [npair] or None). clearance: None or
+    (geom1, geom2), ids or names, scalars or equal-length lists, at most 32 pairs; clearance_min / clearance_weight:
+    a scalar or one value per pair."""
+    import numpy as np
+    cb = _subtree_roots(sys, com_body)
+    if len(cb) != 1:
+        raise ValueError(f"ik_wb takes one com_body, not {len(cb)}")
+    cw = None
+    if com_weight is not None:
+        cw = np.float32(np.broadcast_to(np.asarray(com_weight, np.float64), (3,)))
+        if not (np.isfinite(cw).all() and (cw >= 0).all()):
+            raise ValueError("com_weight must be finite and >= 0")
+    ids1, ids2 = [], []
+    if clearance is not None:
+        g1, g2 = clearance
+        n1, n2 = len(_as_list(g1)), len(_as_list(g2))
+        if max(n1, n2) > MAX_IK_PAIRS:
+            raise ValueError(f"ik_wb takes at most {MAX_IK_PAIRS} clearance pairs, not {max(n1, n2)}")
+        if n1 or n2:
+            ids1, ids2 = geom_pairs(sys, g1, g2)
+    n = len(ids1)
+    cmin = np.float32(np.broadcast_to(np.asarray(clearance_min, np.float64), (n,)))
+    if not (np.isfinite(cmin).all() and (cmin >= 0).all()):
+        raise ValueError("clearance_min must be finite and >= 0")
+    cwt = None
+    if clearance_weight is not None:
+        cwt = np.float32(np.broadcast_to(np.asarray(clearance_weight, np.float64), (n,)))
+        if not (np.isfinite(cwt).all() and (cwt >= 0).all()):
+            raise ValueError("clearance_weight must be finite and >= 0")
+    return cb[0], cw, ids1, ids2, np.ascontiguousarray(cmin), cwt
+
+
+def ik_wb(sys: Model, d: Data, frame=None, target_pos=None, target_quat=None, *, com_target=None, com_body=0,
+          com_weight=None, clearance=None, clearance_min=0.0, clearance_weight=None, offset=None, weight=None,
+          qpos_start=None, qpos_ref=None, dofs=None, iterations: int = 20, damping: float = 1e-3, posture: float = 0.0,
+          max_step: float = 0.0, tol: float = 0.0, limits: bool = True, mask: Optional[torch.Tensor] = None, out=None,
+          _dev=None) -> WBIKResult:
+    """Whole-body inverse kinematics: `ik`'s solve with two more kinds of rows in the same normal equations, still
+    one launch. frame / target_pos / target_quat and the keywords from offset on are ik's; frame may be None (no
+    frame task) when another task exists.
+    com_target [nenv, 3]: brings the centre of mass of the subtree rooted at com_body (an id or a name; 0: the whole
+    model) to this world point; com_weight: one weight >= 0 per world axis, (1, 1, 0) holds the CoM above a point
+    on the ground and leaves its height free. The env's own masses count while per-env model parameters are on.
+    clearance = (geom1, geom2), ids or names as geom_distance's (mjx.collision_pairs(sys) when it has <= 32 pairs):
+    every pair whose signed distance at the iterate is below clearance_min (metres; a scalar or one per pair) gets a
+    row that pushes the distance up to it, weighted by clearance_weight; a pair at or beyond clearance_min adds
+    nothing. A plane - geom pair keeps a foot above the floor. The rows are one-sided penalties of a least-squares
+    step, not constraints of a QP: check WBIKResult.clearance.
+    Returns WBIKResult(qpos, err, niter, com_err, clearance); out: five tensors to write into, all but qpos may be
+    None. Rows of envs with mask <= 0.5 keep what `out` held. Capturable when the targets and out are device
+    tensors. See include/mjx355.h mjl_ik_wb."""
+    import numpy as np
+    dev = d.device
+    if _dev is None:
+        if frame is None:
+            tabs = (None, None, None, None)
+        else:
+            bodies, local, conj, w = ik_tables(sys, frame, offset, weight)
+            tabs = (torch.tensor(bodies, dtype=torch.int32, device=dev), torch.tensor(local, device=dev),
+                    None if conj is None else torch.tensor(conj, device=dev), None if w is None else torch.tensor(w, device=dev))
+        _dev = (tabs, ik_wb_tables(sys, com_body, com_weight, clearance, clearance_min, clearance_weight))
+    (bt, lt, cq, wt), (cb, cw, ids1, ids2, cmin, cwt) = _dev
+    n, npair = (0 if bt is None else bt.shape[0]), len(ids1)
+
+    def arg(t, shape, what):
+        if t is None:
+            return None
+        t = torch.as_tensor(t, dtype=torch.float32).to(dev)
+        if t.dim() == len(shape) - 1 and n == 1 and len(shape) == 3:
+            t = t.unsqueeze(1)
+        if tuple(t.shape) != shape:
+            raise MjlError(f"{what} must have shape {shape}")
+        return t.contiguous()
+    tp = arg(target_pos, (d.nenv, n, 3), "target_pos") if n else None
+    tq = arg(target_quat, (d.nenv, n, 4), "target_quat") if n else None
+    if n and tp is None and tq is None:
+        raise MjlError("ik_wb needs target_pos or target_quat for its frames")
+    if tq is not None and cq is not None:
+        tq = _qmul_t(tq, cq.unsqueeze(0)).contiguous()
+    ct = arg(com_target, (d.nenv, 3), "com_target")
+    if n == 0 and ct is None and npair == 0:
+        raise MjlError("ik_wb needs a frame task, com_target or clearance pairs")
+    qs = arg(qpos_start, (d.nenv, sys.nq), "qpos_start")
+    qr = arg(qpos_ref, (d.nenv, sys.nq), "qpos_ref")
+    shapes = ((d.nenv, sys.nq), (d.nenv, n, 6), (d.nenv,), (d.nenv, 3), (d.nenv, npair))
+    if out is None:
+        new = torch.zeros if mask is not None else torch.empty
+        out = tuple(new(s, dtype=torch.int32 if i == 2 else torch.float32, device=dev) for i, s in enumerate(shapes))
+    out = (tuple(out) + (None,) * 4)[:5]
+    for t, s, what in zip(out, shapes, WBIKResult._fields):
+        if t is None and what == "qpos":
+            raise MjlError("ik_wb needs the qpos output")
+        if t is not None and (tuple(t.shape) != s or t.device != dev):
+            raise MjlError(f"{what} must have shape {s} on {dev}")
+    qo, eo, no, co, cl = out
+    mk = None if mask is None else mask.to(device=dev, dtype=torch.float32).contiguous()
+    dm = ik_dofmask(sys, dofs)
+    host = lambda a, t: None if a is None or len(a) == 0 else (t * len(a))(*a)
+    check(lib().mjl_ik_wb(d.handle, _ptr(mk), n, None if bt is None else _iptr(bt), _ptr(lt), _ptr(tp), _ptr(tq),
+                          _ptr(wt), _ptr(qs), _ptr(qr), dm - (1 << 32) if dm >= 1 << 31 else dm, int(iterations),
+                          float(damping), float(posture), float(max_step), float(tol), abi.IK_LIMITS if limits else 0,
+                          _ptr(qo), _ptr(eo) if n else None, None if no is None else _iptr(no),
+                          cb if ct is not None else -1, _ptr(ct), host(cw, C.c_float), npair, host(ids1, C.c_int32),
+                          host(ids2, C.c_int32), host(cmin, C.c_float), host(cwt, C.c_float), _ptr(co),
+                          _ptr(cl) if npair else None, _stream()))
+    return WBIKResult(qo, eo, no, co, cl)
+
+
 def step_vjp_full(sys: Model, d: Data, g_qpos: torch.Tensor, g_qvel: torch.Tensor, g_qacc_ws: torch.Tensor):
     """step_vjp with the carried warm start (mjl_step_vjp_full): cotangents of (qpos', qvel',
     qacc_warmstart') -> (qpos, qvel, qacc_warmstart, ctrl)."""
